@@ -21,7 +21,14 @@ traversals / timed wall time (whole job, all GPUs).  The graph is generated on
 the GPUs with the Graph500 Kronecker parameters (a=.57 b=.19 c=.19, edge
 factor 16, scrambled vertex labels): synthetic by construction (no dataset).
 
-Honesty fields:
+A plain run does only that: build the graph, warm up, time the K traversals,
+write them with ``--dump-outputs DIR`` and print the record.  Everything below
+that takes traversals of its own (the int32-level pass, validation, held-out
+roots, secondary graphs, the per-level profile, ``--per-level``,
+``--baseline-live``, ``--allow-fallback``) runs only with ``--full``; without
+it those fields are null.
+
+Honesty fields (``--full``):
   * ``level_state_dtype``: the engine keeps one-byte levels during a traversal
     (widened to the reference's int32 when read, outside the timer);
     ``value_int32_levels`` is a second timed pass of the same K roots with
@@ -136,6 +143,16 @@ def parse_args(argv=None):
     ap.add_argument("--secondary-roots", type=int, default=16)
     ap.add_argument("--spawn-timeout", type=float, default=1500.0,
                     help="self-spawned ranks: seconds before the children are killed")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline pass also run everything else the record can hold: the int32-level "
+                         "pass, validation of every timed root, the held-out roots, the secondary graphs, the "
+                         "per-level profile (and --per-level / --baseline-live / --allow-fallback); without it "
+                         "those fields are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed traversal computed as DIR/<name>.npy: "
+                         "levels.npy (float32 per-vertex levels, -1 = unreached; a fixed seeded sample of the "
+                         "vertices, their ids in level_vertices.npy, when the graph is too large) and "
+                         "last_step.npy (float64: source, reached vertices, traversed edges, depth)")
     return ap.parse_args(argv)
 
 
@@ -202,6 +219,34 @@ def timed_pass(bfs, rt, roots):
     rt.barrier()
     wall_ms = (time.perf_counter() - t_start) * 1e3
     return results, rt.comm.max_host(wall_ms)
+
+
+DUMP_MAX_LEVELS = 4 << 20  # levels written at most: 16 MiB of float32 (+ 32 MiB of vertex ids as float64)
+
+
+def dump_outputs(out_dir: str, bfs, rank: int, last):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- the per-vertex levels of that traversal (collective gather; rank 0
+    writes) and its totals.  Graph, roots and the vertex sample depend only on
+    the arguments, so two builds run with the same arguments write comparable
+    files."""
+    import numpy as np
+
+    from distributed_cuda_bfs_amd import UNREACHED
+
+    levels = bfs.levels()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    if levels.size > DUMP_MAX_LEVELS:
+        idx = np.sort(np.random.default_rng(20260101).integers(0, levels.size, size=DUMP_MAX_LEVELS))
+        np.save(os.path.join(out_dir, "level_vertices.npy"), idx.astype(np.float64))
+        levels = levels[idx]
+    lv = levels.astype(np.float32)
+    lv[levels == UNREACHED] = -1.0
+    np.save(os.path.join(out_dir, "levels.npy"), lv)
+    np.save(os.path.join(out_dir, "last_step.npy"),
+            np.array([last.source, last.reached, last.edges, last.depth], dtype=np.float64))
 
 
 def validated_pass(bfs, rt, roots):
@@ -330,10 +375,13 @@ def main(argv=None) -> int:
             res = bfs.run(r)
             log(f"warmup root {r}: {res.ms:.3f} ms, {res.gteps:.2f} GTEPS, depth {res.depth}")
         results, wall_ms = timed_pass(bfs, rt, timed)
+        if args.dump_outputs:
+            # before anything else traverses: the engine holds the last timed step's levels
+            dump_outputs(args.dump_outputs, bfs, rank, results[-1])
         # Second timed pass: the same roots with 32-bit levels written by the kernels.
         narrow = bool(dict(bfs.engine.get_options()).get("narrow_levels", 0)) and args.mode in ("td", "bu", "do")
         value_i32 = None
-        if narrow and not args.no_int32_pass:
+        if args.full and narrow and not args.no_int32_pass:
             bfs.engine.set_option("narrow_levels", 0)
             bfs.run(warm[0] if warm else timed[0])
             res32, wall32 = timed_pass(bfs, rt, timed)
@@ -345,7 +393,7 @@ def main(argv=None) -> int:
         # the timed traversal's (reached vertices, traversed edges, depth) --
         # so the validated traversal is the one that was timed.
         validated, n_valid = None, 0
-        if not args.no_validate:
+        if args.full and not args.no_validate:
             for r, tr in zip(timed, results):
                 res = bfs.run(r)
                 ok = bfs.validate(r)
@@ -385,7 +433,7 @@ def main(argv=None) -> int:
     bfs_ms = sum(r.ms for r in results)
     value = edges / (wall_ms * 1e6)
 
-    if args.per_level:
+    if args.full and args.per_level:
         order = sorted(results, key=lambda r: r.ms)
         bfs.engine.phase_timing = True
         profs = [bfs.run(order[0].source), bfs.run(order[-1].source)]
@@ -402,7 +450,7 @@ def main(argv=None) -> int:
     # the driver's K roots.
     heldout = None
     fast_mode = args.mode in ("td", "bu", "do")  # (ref / simple / scan take seconds per root)
-    if args.heldout_roots > 0 and fast_mode:
+    if args.full and args.heldout_roots > 0 and fast_mode:
         hroots = bfs.sample_roots(args.heldout_roots, seed=args.heldout_seed)
         if hroots:
             hv, hms, hok, hres = validated_pass(bfs, rt, hroots)
@@ -413,7 +461,9 @@ def main(argv=None) -> int:
             if hok != len(hroots):
                 validated = False
     secondary = None
-    if args.secondary == "auto":
+    if not args.full:
+        args.secondary = "none"
+    elif args.secondary == "auto":
         args.secondary = "4847571:68993773" if rt.is_gpu else "none"
     if args.secondary and args.secondary != "none" and not args.graph and fast_mode:
         un, _, um = args.secondary.partition(":")
@@ -448,14 +498,18 @@ def main(argv=None) -> int:
     # One extra (untimed) traversal of the median timed root with per-level
     # device events: where the time goes (collectives vs kernels) at this N.
     med = sorted(results, key=lambda r: r.ms)[len(results) // 2]
-    bfs.engine.phase_timing = True
-    prof = bfs.run(med.source)
-    bfs.engine.phase_timing = False
-    level_profile = [[lv["dir"], round(lv["ms"], 4), round(lv.get("comm_ms", 0.0), 4)] for lv in prof.levels]
+    prof, level_profile = None, None
+    if args.full:
+        bfs.engine.phase_timing = True
+        prof = bfs.run(med.source)
+        bfs.engine.phase_timing = False
+        level_profile = {"root": med.source, "columns": ["dir", "ms", "comm_ms"],
+                         "levels": [[lv["dir"], round(lv["ms"], 4), round(lv.get("comm_ms", 0.0), 4)]
+                                    for lv in prof.levels]}
 
     baseline = args.baseline_gteps
     baseline_src = "--baseline-gteps" if baseline else None
-    if args.baseline_live and args.mode != "ref":
+    if args.full and args.baseline_live and args.mode != "ref":
         mode = bfs.mode
         bfs.mode = "ref"
         ref_roots = timed[:max(1, args.baseline_roots)]
@@ -479,6 +533,7 @@ def main(argv=None) -> int:
             "warmup": args.warmup,
             "ms_per_step": round(wall_ms / args.steps, 4),
             "higher_is_better": True,
+            "full": args.full,
             "scaling": "weak" if args.weak else "strong",
             "vs_baseline": (round(value / baseline, 2) if baseline else None),
             "baseline": baseline_src,
@@ -520,9 +575,9 @@ def main(argv=None) -> int:
             "comm_inner_ops": getattr(rt.comm, "inner_ops", None),
             # chains of the profiled traversal whose frontier the producing
             # kernels pushed into the peers' windows (direct_frontier)
-            "pushed_chains": sum(1 for c in getattr(prof, "chains", []) if len(c) > 4 and c[4]),
+            "pushed_chains": (sum(1 for c in prof.chains if len(c) > 4 and c[4]) if prof else None),
             # ... and its bottom-up chains with the hub cut's launches
-            "cut_chains": sum(1 for c in getattr(prof, "chains", []) if len(c) > 7 and c[7]),
+            "cut_chains": (sum(1 for c in prof.chains if len(c) > 7 and c[7]) if prof else None),
             "heldout": heldout,
             "secondary": secondary,
             "devices": [f"{'hip' if rt.is_gpu else 'cpu'}:{d}" for d in devices],
@@ -540,8 +595,7 @@ def main(argv=None) -> int:
             "generate_s": round(gen_s, 3),
             # peak resident host memory of rank 0's process (graph build included)
             "host_peak_rss_gb": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2**20, 3),
-            "level_profile": {"root": med.source, "levels": level_profile,
-                              "columns": ["dir", "ms", "comm_ms"]},
+            "level_profile": level_profile,
             # the timed traversal of the same root, from the device clock the
             # kernels stamp (device loop only): level time and the idle gap
             # before its first kernel

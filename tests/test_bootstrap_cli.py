@@ -134,7 +134,7 @@ def test_cli_roots_and_cache(tmp_path):
 
 def test_bench_contract_cpu():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--device", "cpu", "--scale", "10",
-                          "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=300)
+                          "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -154,6 +154,44 @@ def test_bench_contract_cpu():
     assert rec["value"] == pytest.approx(rec["traversed_edges_mean"] * 3 / (rec["ms_per_step"] * 3 * 1e6), rel=1e-2)
 
 
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_and_dump_outputs_cpu(tmp_path, gpus):
+    """Without --full the bench only times its steps: the headline fields are
+    there, everything measured by traversals of its own is null.
+    --dump-outputs writes the last timed traversal's levels (the oracle's)
+    and totals, the same from run to run."""
+    import distributed_cuda_bfs_amd as dbfs
+
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    recs = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--device", "cpu",
+                              "--scale", "10", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)],
+                             capture_output=True, text=True, timeout=300, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert rec["full"] is False and rec["steps"] == 3 and rec["n_gpus"] == gpus
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["unit"] == "GTEPS" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "uint8 levels (int32 on read)"
+    assert rec["value"] == pytest.approx(rec["traversed_edges_mean"] * 3 / (rec["ms_per_step"] * 3 * 1e6), rel=1e-2)
+    for k in ("validated", "validated_roots", "value_int32_levels", "heldout", "secondary", "level_profile"):
+        assert rec[k] is None, k
+    assert sorted(os.listdir(tmp_path / "a")) == ["last_step.npy", "levels.npy"]
+    levels, last = np.load(tmp_path / "a" / "levels.npy"), np.load(tmp_path / "a" / "last_step.npy")
+    assert levels.dtype == np.float32 and last.dtype == np.float64
+    exp, _ = dbfs.cpu_bfs(dbfs.host_csr_from_params(dbfs.rmat_params(10, 16, 1)), int(last[0]))
+    reached = exp != dbfs.UNREACHED
+    assert np.array_equal(levels, np.where(reached, exp, -1).astype(np.float32))
+    assert last.shape == (4,) and last[1] == np.count_nonzero(reached) and last[2] > 0 and last[3] > 0
+    assert np.array_equal(levels, np.load(tmp_path / "b" / "levels.npy"))
+    assert np.array_equal(last, np.load(tmp_path / "b" / "last_step.npy"))
+
+
 def test_bench_self_spawn_cpu():
     """``bench.py --gpus 3`` without a launcher starts 3 rank processes itself
     (no torchrun): one JSON line from rank 0, the communicator really formed 3
@@ -162,7 +200,7 @@ def test_bench_self_spawn_cpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "3", "--device", "cpu",
-                          "--scale", "10", "--steps", "3", "--warmup", "1"],
+                          "--scale", "10", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -192,7 +230,7 @@ def test_bench_weak_scaling_cpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--device", "cpu",
-                          "--scale", "9", "--weak", "--steps", "2", "--warmup", "1", "--no-int32-pass"],
+                          "--scale", "9", "--weak", "--steps", "2", "--warmup", "1", "--no-int32-pass", "--full"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
@@ -209,7 +247,7 @@ def test_bench_graph_file_cpu(tmp_path):
     e = rng.integers(0, n, size=(m, 2))
     path.write_text(f"{n} {m}\n" + "".join(f"{u} {v}\n" for u, v in e))
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--device", "cpu", "--graph", str(path),
-                          "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=300)
+                          "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert rec["config"]["model"] == "g.txt" and rec["config"]["vertices"] == n
@@ -222,7 +260,7 @@ def test_bench_uniform_graph_cpu():
     # soc-LiveJournal1-sized stand-in without the 1 GB text file); no RMAT
     # baseline applies to it
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--device", "cpu", "--uniform", "3001:20000",
-                          "--mode", "td", "--steps", "2", "--warmup", "1", "--no-int32-pass"],
+                          "--mode", "td", "--steps", "2", "--warmup", "1", "--no-int32-pass", "--full"],
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -240,7 +278,7 @@ def test_bench_torchrun_multiprocess_cpu(nproc, mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
            "--gpus", str(nproc), "--device", "cpu", "--scale", "10", "--steps", "2", "--warmup", "1",
-           "--mode", mode]
+           "--mode", mode, "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

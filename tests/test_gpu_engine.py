@@ -501,7 +501,7 @@ def test_multiprocess_ranks_share_one_gpu_tcp():
     env = dict(os.environ, DBFS_DEVICE="0", DBFS_COMM="tcp")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--scale", "18",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -521,7 +521,7 @@ def test_bench_self_spawned_ranks_share_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--scale", "18", "--steps", "3",
-           "--warmup", "1"]
+           "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -773,7 +773,7 @@ def test_peer_comm_two_ranks_share_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--scale", "18", "--steps", "4",
-           "--warmup", "1"]
+           "--warmup", "1", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -984,7 +984,7 @@ def test_peer_comm_four_ranks_share_one_gpu_rmat20():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "4", "--scale", "20", "--steps", "4",
-           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "8", "--secondary", "none"]
+           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "8", "--secondary", "none", "--full"]
     out = _run_group(cmd, env, 100)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1010,7 +1010,7 @@ def test_peer_comm_eight_ranks_share_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "8", "--scale", "19", "--steps", "4",
-           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "8", "--secondary", "none"]
+           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "8", "--secondary", "none", "--full"]
     out = _run_group(cmd, env, 140)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1039,7 +1039,7 @@ def test_peer_fused_forms_share_one_gpu(ranks):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--scale", "19", "--steps",
-           "4", "--warmup", "1", "--no-int32-pass", "--heldout-roots", "8", "--secondary", "none"]
+           "4", "--warmup", "1", "--no-int32-pass", "--heldout-roots", "8", "--secondary", "none", "--full"]
     out = _run_group(cmd, env, 140)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1063,7 +1063,7 @@ def test_peer_late_rank_completes():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "4", "--scale", "18", "--steps", "3",
-           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "0", "--secondary", "none"]
+           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "0", "--secondary", "none", "--full"]
     out = _run_group(cmd, env, 110)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1126,7 +1126,7 @@ def test_transport_setup_failures_fall_back(fault, comm):
     if "rccl_init" in fault:
         env["DBFS_TRY_RCCL"] = "1"
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "2", "--scale", "17", "--steps", "3",
-           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "0", "--secondary", "none"]
+           "--warmup", "1", "--no-int32-pass", "--heldout-roots", "0", "--secondary", "none", "--full"]
     out = _run_group(cmd, env, 110)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1275,7 +1275,7 @@ def test_peer_direct_exchange_long_chain(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "2", "--graph", str(path), "--steps", "3",
-           "--warmup", "1", "--no-int32-pass"]
+           "--warmup", "1", "--no-int32-pass", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -1362,7 +1362,7 @@ def _bench_peer(args, timeout=200, **env_extra):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py")] + args + ["--heldout-roots", "0", "--secondary",
-                                                                          "none", "--no-int32-pass"]
+                                                                          "none", "--no-int32-pass", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -4,9 +4,12 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp; mkdir -p gpurun_out
 ROOT=$PWD; T=${TAG:-cab}; d=/tmp/cab_tree
 rm -rf $d && mkdir -p $d && tar -C commit_ab_tree -cf - . | tar -C $d -xf - && (cd $d && make -j16 > $ROOT/gpurun_out/${T}_make.log 2>&1) || { tail -20 gpurun_out/${T}_make.log; exit 1; }
+USER_ARGS=${BENCH_ARGS}
 for rep in 1 2; do
   for side in A B; do
     dir=$ROOT; [ $side = B ] && dir=$d
+    # held-out and int32 passes need --full (a commit from before that option runs them unasked)
+    BENCH_ARGS=$USER_ARGS; grep -q -e '"--full"' $dir/bench.py && BENCH_ARGS="--full $USER_ARGS"
     timeout -k 10 300 python3 -u $dir/bench.py --steps 16 --warmup 2 --secondary none ${BENCH_ARGS} > gpurun_out/${T}_$side$rep.json 2> gpurun_out/${T}_$side$rep.err || { tail -20 gpurun_out/${T}_$side$rep.err; exit 1; }
     python3 - gpurun_out/${T}_$side$rep.json $side <<'PY'
 import json, sys

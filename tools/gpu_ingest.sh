@@ -23,7 +23,7 @@ kill $hb
 t1=$(date +%s)
 ls -la "$F"; echo "write_s $((t1 - t0))"
 ( while sleep 20; do echo "[ingest] bench running"; done ) & hb=$!
-timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --graph "$F" --steps ${STEPS:-8} --warmup 2 --no-int32-pass ${BENCH_ARGS} \
+timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py --graph "$F" --steps ${STEPS:-8} --warmup 2 --no-int32-pass --full ${BENCH_ARGS} \
   > gpurun_out/ingest.json 2> gpurun_out/ingest.err; rc=$?
 kill $hb
 rm -f "$F"

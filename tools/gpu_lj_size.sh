@@ -20,7 +20,7 @@ dbfs.native.write_generated_edge_list(sys.argv[1], dbfs.uniform_params(4847571, 
 " "$F" || { echo "write failed"; exit 1; }
 ls -la "$F"
 for mode in td do; do
-  timeout -k 10 400 python bench.py --graph "$F" --mode $mode --steps 16 --warmup 3 > $O/bench_$mode.json 2> $O/bench_$mode.log \
+  timeout -k 10 400 python bench.py --graph "$F" --mode $mode --steps 16 --warmup 3 --full > $O/bench_$mode.json 2> $O/bench_$mode.log \
     || { tail -20 $O/bench_$mode.log; rm -f "$F"; exit 1; }
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], 'GTEPS', d['ms_per_step'], 'ms/step', d['validated_roots'], 'int32', d.get('value_int32_levels'), 'load', d['generate_s'], 's rss', d['host_peak_rss_gb'])" $O/bench_$mode.json $mode
 done

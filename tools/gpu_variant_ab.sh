@@ -8,6 +8,7 @@ ROOT=$PWD
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 : > gpurun_out/variant_ab.txt
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the per-level profile printed below is measured with --full only)
 IFS='|' read -ra FS <<< "${FLAGSETS:-}"
 i=0
 for f in "${FS[@]}"; do
