@@ -695,7 +695,7 @@ class CpuBackend final : public Backend {
     nz_ro[k] = rows > 0 ? ro[rows] : 0;
     (void)pref;
   }
-  void nz_records(const eid_t* ro, const vid_t* head, int64_t rows, const eid_t* pref, NzRec* rec,
+  void nz_records(const eid_t* ro, const vid_t* head, int64_t rows, const eid_t* pref, NzRec* rec, uint16_t* loc,
                   eid_t* unit_base) override {
     const int64_t nunits = div_up(std::max<int64_t>(rows, 1), kUnitVertices);
     for (int64_t u = 0; u <= nunits; ++u) unit_base[u] = ro[std::min<int64_t>(u * kUnitVertices, rows)];
@@ -704,6 +704,7 @@ class CpuBackend final : public Backend {
       if (ro[v + 1] > ro[v]) {
         rec[k].off = static_cast<uint32_t>(ro[v] - unit_base[v / kUnitVertices]);
         rec[k].head = head[v];
+        loc[k] = static_cast<uint16_t>(v % kUnitVertices);
         ++k;
       }
     }

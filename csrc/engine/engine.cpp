@@ -301,6 +301,7 @@ ShardView DeviceGraph::view() const {
   v.nz_row_off = nz_row_off_.data();
   v.nz_head = nz_head_.data();
   v.nz_rec = nz_rec_.data();
+  v.nz_loc = nz_loc_.data();
   v.unit_base = unit_base_.data();
   if (td_nhubs_ > 0) {
     v.td_col = td_col_.data();
@@ -321,6 +322,17 @@ HostCSR DeviceGraph::to_host() const {
   be_->to_host(h.row_off.data(), row_off_.data(), h.row_off.size() * sizeof(eid_t));
   if (nnz_) be_->to_host(h.col.data(), col_.data(), h.col.size() * sizeof(vid_t));
   return h;
+}
+
+std::vector<uint16_t> DeviceGraph::debug_nz_loc() const {
+  std::vector<uint16_t> out;
+  if (!nz_loc_.data() || !nz_rec_.data()) return out;
+  const int64_t words = div_up(std::max<int64_t>(rows_, 1), kWordBits);
+  eid_t nzrows = 0;
+  be_->to_host(&nzrows, nz_pref_.data() + words, sizeof(eid_t));
+  out.resize(static_cast<size_t>(nzrows));
+  if (nzrows) be_->to_host(out.data(), nz_loc_.data(), out.size() * sizeof(uint16_t));
+  return out;
 }
 
 std::vector<eid_t> DeviceGraph::degrees_of(const std::vector<int64_t>& local_rows) const {
@@ -475,17 +487,21 @@ void DeviceGraph::build_nz_view() {
   be_->nz_fill(row_off_.data(), head_.data(), rows_, nz_pref_.data(), nz_row_off_.data(), nz_head_.data());
   // packed records, when every unit's edges fit 32-bit relative offsets
   nz_rec_ = DBuf<NzRec>();
+  nz_loc_ = DBuf<uint16_t>();
   unit_base_ = DBuf<eid_t>();
   if (rows_ <= 0) return;
   const int64_t nunits = div_up(rows_, kUnitVertices);
   unit_base_ = DBuf<eid_t>(*be_, static_cast<size_t>(nunits + 1));
   nz_rec_ = DBuf<NzRec>(*be_, static_cast<size_t>(std::max<eid_t>(nzrows, 1)));
-  be_->nz_records(row_off_.data(), head_.data(), rows_, nz_pref_.data(), nz_rec_.data(), unit_base_.data());
+  nz_loc_ = DBuf<uint16_t>(*be_, static_cast<size_t>(std::max<eid_t>(nzrows, 1)));
+  be_->nz_records(row_off_.data(), head_.data(), rows_, nz_pref_.data(), nz_rec_.data(), nz_loc_.data(),
+                  unit_base_.data());
   std::vector<eid_t> ub(static_cast<size_t>(nunits + 1));
   be_->to_host(ub.data(), unit_base_.data(), ub.size() * sizeof(eid_t));
   for (int64_t u = 0; u < nunits; ++u)
     if (ub[static_cast<size_t>(u + 1)] - ub[static_cast<size_t>(u)] >= (eid_t(1) << 32)) {
       nz_rec_ = DBuf<NzRec>();
+      nz_loc_ = DBuf<uint16_t>();
       unit_base_ = DBuf<eid_t>();
       break;
     }

@@ -68,6 +68,13 @@ struct ShardView {
   // the unit's last non-empty row.  8 bytes per row instead of the view's
   // 8-byte offset + 4-byte head; present when every unit spans < 2^32 edges.
   const struct NzRec* nz_rec = nullptr;
+  // Way back from a record to its vertex (present exactly when nz_rec is):
+  // nz_loc[k] = position (0..4095) of row k's vertex inside its unit, so row
+  // k of unit U is vertex 4096 U + nz_loc[k].  2 bytes per non-empty row; a
+  // static property of the graph.  The bottom-up kernels' record-order walk
+  // reads a unit's records [nz_pref[64 U], nz_pref[64 U + 64]) in order with
+  // it, instead of ranking each unvisited vertex among the unit's rows.
+  const uint16_t* nz_loc = nullptr;
   const eid_t* unit_base = nullptr;  // ceil(rows / 4096) + 1 entries: row_off of each unit's first vertex
   // Top-down copy of col (same layout, neighbour-id order) with the
   // td_nhubs highest-degree vertices encoded as kHubFlag | index
@@ -1147,10 +1154,11 @@ class Backend {
   virtual void nz_word_counts(const eid_t* row_off, int64_t rows, int64_t words, eid_t* counts) = 0;
   virtual void nz_fill(const eid_t* row_off, const vid_t* head, int64_t rows, const eid_t* nz_pref, eid_t* nz_row_off,
                        vid_t* nz_head) = 0;
-  // Packed records of the view (ShardView::nz_rec) and the unit bases
-  // (ceil(rows / 4096) + 1 entries).
+  // Packed records of the view (ShardView::nz_rec), their vertices' positions
+  // in their units (ShardView::nz_loc) and the unit bases (ceil(rows / 4096)
+  // + 1 entries).
   virtual void nz_records(const eid_t* row_off, const vid_t* head, int64_t rows, const eid_t* nz_pref, NzRec* rec,
-                          eid_t* unit_base) = 0;
+                          uint16_t* loc, eid_t* unit_base) = 0;
   // out[e] = kHubFlag | hub_idx[col[e]] for hub neighbours, else col[e].
   virtual void encode_hub_cols(const vid_t* col, int64_t nnz, const uint32_t* hub_idx, vid_t* out) = 0;
   // Hubs = vertices of degree >= min_deg (deg_all has n entries): hub_vertex

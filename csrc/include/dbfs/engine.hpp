@@ -60,6 +60,9 @@ class DeviceGraph {
   int64_t nnz() const { return nnz_; }
   int64_t input_edges() const { return input_edges_; }
   std::vector<eid_t> degrees_of(const std::vector<int64_t>& local_rows) const;
+  // Debug / tests: host copy of ShardView::nz_loc, one entry per non-empty
+  // row (empty when the shard has no packed records).
+  std::vector<uint16_t> debug_nz_loc() const;
   // Reorder every row hub-first (neighbour degree descending); collective over
   // `comm` (all ranks need every vertex's degree).  One-time preprocessing.
   // With `hubs`, the (up to kMaxHubs) highest-degree vertices of the graph are
@@ -106,6 +109,7 @@ class DeviceGraph {
   int64_t td_nhubs_ = 0;
   DBuf<eid_t> nz_pref_, nz_row_off_;
   DBuf<NzRec> nz_rec_;      // packed view records (empty when a unit spans >= 2^32 edges)
+  DBuf<uint16_t> nz_loc_;   // ShardView::nz_loc (present exactly when nz_rec_ is)
   DBuf<eid_t> unit_base_;
   void build_nz_view();
   DBuf<eid_t> row_off_;

@@ -67,6 +67,15 @@ constexpr int kCutLevels = 1, kCutClaims = 2;  // hub-cut variants (bu_hub_kerne
 // probing step).  LDS: 16 waves x kBuQueue x 8 B next to the hub bits
 // (kMaxHubs / 8 B) and the 8 KiB result words, two workgroups per CU.
 constexpr int kBuQueue = 64;
+// Threshold of the record-order walk (bu_wave_compact): taken by a unit with
+// at least kRecWalkNum / kRecWalkDen of its non-empty rows unvisited.
+#ifndef DBFS_REC_WALK_NUM
+#define DBFS_REC_WALK_NUM 1
+#endif
+#ifndef DBFS_REC_WALK_DEN
+#define DBFS_REC_WALK_DEN 2
+#endif
+constexpr int kRecWalkNum = DBFS_REC_WALK_NUM, kRecWalkDen = DBFS_REC_WALK_DEN;
 static_assert(kBuQueue <= kWave, "one queued row per lane per flush");
 
 #ifdef DBFS_BU_STATS
@@ -190,9 +199,14 @@ __device__ __forceinline__ bool bu_scan_row(const BuArgs& a, eid_t rs, eid_t e, 
 // popcount prefix) and processed 64 at a time, one per lane, whatever word
 // they sit in -- the per-step cost is a chain of dependent memory round trips
 // nearly independent of how many lanes are active, so steps =
-// ceil(unvisited / 64) instead of the words with any unvisited vertex.  Per
-// step: row bounds and head (prefetched one step ahead), head probe, then the
-// row scan.  Found bits are OR-ed into a per-wave LDS copy of the result words
+// ceil(unvisited / 64) instead of the words with any unvisited vertex (the
+// compaction walk).  A whole unit most of whose non-empty rows are unvisited
+// (kRec, kWords = 64: the first bottom-up levels) is walked in record order
+// instead: 64 consecutive records of ShardView::nz_rec per step, their
+// vertices from nz_loc, the visited ones dropped -- addresses affine in
+// (step, lane), no rank search in front of a record (see the walk's choice
+// below).  Per step: row bounds and head (prefetched one step ahead; the
+// record walk two), head probe, then the row scan.  Found bits are OR-ed into a per-wave LDS copy of the result words
 // (s_res), written out once with the visited update; levels and unit
 // statistics are written directly (no separate update pass).
 // kQueue > 0: rows whose head probe failed are not scanned in the step that
@@ -359,12 +373,32 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
     }
   };
   const int nb = (total + kWave - 1) / kWave;
-  int n_loc;
-  eid_t n_rs;
-  uint32_t n_len;
-  vid_t n_u;
-  fetch(0, n_loc, n_rs, n_len, n_u);
-  if (!head) n_u = n_len ? col[n_rs] : 0u;
+  // The walk, chosen per unit (wave-uniform).  Record order -- the unit's
+  // non-empty rows [k0, u_nzend) as they lie in nz_rec, their vertices from
+  // nz_loc, the visited ones dropped -- when at least kRecWalkNum /
+  // kRecWalkDen of them are unvisited: no rank search and no dependent load
+  // in front of a record, but a step per 64 rows whatever their state.
+  // Otherwise the compaction walk: a step per 64 unvisited vertices, each
+  // ranked among the unit's rows (fetch).  Same rows examined either way.
+  constexpr bool kRecWalk = kRec && kWords == kUnitWords;
+  bool rec_walk = false;
+  int64_t k0 = 0;
+  int nrec = 0;
+  if constexpr (kRecWalk) {
+    // (w0 is inside the view: the unit has an unvisited vertex; clamped all the same)
+    const int64_t row_words = (a.g.rows + kWordBits - 1) / kWordBits;
+    k0 = static_cast<int64_t>(readlane64(static_cast<unsigned long long>(a.g.nz_pref[min(w0, row_words)]), 0));
+    nrec = static_cast<int>(min(max(u_nzend - k0, int64_t(0)), static_cast<int64_t>(kUnitVertices)));
+    rec_walk = a.g.nz_loc != nullptr && total * kRecWalkDen >= nrec * kRecWalkNum;
+  }
+  int n_loc = -1;
+  eid_t n_rs = 0;
+  uint32_t n_len = 0;
+  vid_t n_u = 0;
+  if (!rec_walk) {
+    fetch(0, n_loc, n_rs, n_len, n_u);
+    if (!head) n_u = n_len ? col[n_rs] : 0u;
+  }
   int cnt32 = 0;
   // deferred row scans (kQueue): base = the unit's first row offset
   eid_t q_base = 0;
@@ -412,11 +446,10 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
     settle(lane < qn && f, ql, qrs, qe);
     qn = 0;
   };
-  for (int b = 0; b < nb; ++b) {
-    const int loc = n_loc;
-    const eid_t rs = n_rs, e = n_rs + n_len;
-    const vid_t u0 = n_u;
-    fetch(b + 1, n_loc, n_rs, n_len, n_u);  // in flight during this batch's probes
+  // One step's 64 rows, one per lane (loc < 0: none; wave-uniform call): head
+  // probe, then the row scan (deferred with kQueue).  `ahead` issues the loads
+  // of a later step's rows, in flight during this step's probes.
+  auto step = [&](int loc, eid_t rs, eid_t e, vid_t u0, auto&& ahead) {
     bool found = false;
     bool cut_row = false;  // (kCut) a hub-first row with a non-hub head: nothing to scan
     if constexpr (kCut) {
@@ -428,7 +461,7 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
     BU_STAT(0, 1);
     BU_STAT(1, __popcll(__ballot(loc >= 0)));
     BU_STAT(2, __popcll(__ballot(found)));
-    if (!head) n_u = n_len ? col[n_rs] : 0u;
+    ahead();
     if constexpr (kQueue > 0) {
       // found by the head: settled now; unresolved rows with more neighbours
       // are queued (huge rows / spans scanned in place)
@@ -456,6 +489,64 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
       found = bu_scan_row<kHub, (kCut != 0)>(a, rs, e, found || cut_row, s_hub, cut) && !cut_row;
       BU_STAT(7, __popcll(__ballot(found)));
       settle(found, loc, rs, e);
+    }
+  };
+  if (rec_walk) {
+    if constexpr (kRecWalk) {
+      // Record-order walk: lane l of step b owns record k0 + 64 b + l.  The
+      // next step's records are held too (they supply lane 63's row end) and
+      // the ones after them are loaded behind this step's probes; lanes past
+      // the unit's records hold off = u_span, so its last row ends there.
+      // (wave-uniform bases, one 32-bit lane index: scalar address + offset)
+      const NzRec* __restrict__ rp = nz_rec + k0;
+      const uint16_t* __restrict__ lp = a.g.nz_loc + k0;
+      const int nrb = (nrec + kWave - 1) / kWave;
+      uint32_t c_off, n_off;
+      vid_t c_u, n_hd;
+      int c_l, n_l;
+      auto load = [&](int b, uint32_t& off, vid_t& hd, int& l) {
+        off = u_span;
+        hd = 0;
+        l = 0;
+        const uint32_t i = static_cast<uint32_t>(b * kWave + lane);
+        if (i < static_cast<uint32_t>(nrec)) {
+          const NzRec r = rp[i];
+          off = r.off;
+          hd = r.head;
+          l = lp[i];
+        }
+      };
+      load(0, c_off, c_u, c_l);
+      load(1, n_off, n_hd, n_l);
+      for (int b = 0; b < nrb; ++b) {
+        const bool act = b * kWave + lane < nrec;
+        DBFS_DCHECK(!act || k0 + b * kWave + lane < u_nzend, 12, k0 + b * kWave + lane);
+        DBFS_DCHECK(!act || c_l < kUnitVertices, 13, c_l);
+        // row end: the next lane's start; lane 63: the next step's first
+        const uint32_t nx = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(n_off)));
+        const uint32_t dn = static_cast<uint32_t>(__shfl_down(static_cast<int>(c_off), 1, kWave));
+        const uint32_t end = lane == kWave - 1 ? nx : dn;
+        // live: the vertex's bit in the unvisited word its lane holds
+        const word_t uw = static_cast<word_t>(__shfl(static_cast<long long>(um), (c_l >> 6) & (kWave - 1), kWave));
+        const bool live = act && ((uw >> (c_l & 63)) & 1ull);
+        const int loc = live ? c_l : -1;
+        const eid_t rs = live ? u_base + c_off : 0, e = live ? u_base + end : 0;
+        const vid_t u0 = c_u;
+        c_off = n_off;
+        c_u = n_hd;
+        c_l = n_l;
+        step(loc, rs, e, u0, [&]() { load(b + 2, n_off, n_hd, n_l); });
+      }
+    }
+  } else {
+    for (int b = 0; b < nb; ++b) {
+      const int loc = n_loc;
+      const eid_t rs = n_rs, e = n_rs + n_len;
+      const vid_t u0 = n_u;
+      fetch(b + 1, n_loc, n_rs, n_len, n_u);  // in flight during this batch's probes
+      step(loc, rs, e, u0, [&]() {
+        if (!head) n_u = n_len ? col[n_rs] : 0u;
+      });
     }
   }
   if constexpr (kQueue > 0) {

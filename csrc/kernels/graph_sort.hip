@@ -240,10 +240,11 @@ __global__ __launch_bounds__(kBlock) void nz_fill_kernel(const eid_t* __restrict
 }
 
 // Packed records of the non-empty-row view: row k of unit U (vertices
-// [4096 U, 4096 U + 4096)) -> {row start - unit_base[U], head}.
+// [4096 U, 4096 U + 4096)) -> {row start - unit_base[U], head}, and
+// loc[k] = the vertex's position in the unit (ShardView::nz_loc).
 __global__ __launch_bounds__(kBlock) void nz_rec_kernel(const eid_t* __restrict__ ro, const vid_t* __restrict__ head,
                                                        int64_t rows, int64_t words, const eid_t* __restrict__ pref,
-                                                       NzRec* __restrict__ rec) {
+                                                       NzRec* __restrict__ rec, uint16_t* __restrict__ loc) {
   const int64_t w = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + (threadIdx.x >> 6);
   if (w >= words) return;
   const int64_t v = w * kWave + lane_id();
@@ -255,6 +256,7 @@ __global__ __launch_bounds__(kBlock) void nz_rec_kernel(const eid_t* __restrict_
     r.off = static_cast<uint32_t>(ro[v] - ro[(v / kUnitVertices) * kUnitVertices]);
     r.head = head[v];
     rec[k] = r;
+    loc[k] = static_cast<uint16_t>(v % kUnitVertices);
   }
 }
 
@@ -320,12 +322,13 @@ void nz_fill(const eid_t* row_off, const vid_t* head, int64_t rows, int64_t word
 }
 
 void nz_records(const eid_t* row_off, const vid_t* head, int64_t rows, int64_t words, const eid_t* nz_pref,
-                NzRec* rec, eid_t* unit_base, hipStream_t st) {
+                NzRec* rec, uint16_t* loc, eid_t* unit_base, hipStream_t st) {
   if (rows <= 0) return;
   const int64_t nunits = (rows + kUnitVertices - 1) / kUnitVertices;
   unit_base_kernel<<<static_cast<unsigned>((nunits + 1 + kBlock - 1) / kBlock), kBlock, 0, st>>>(row_off, rows, nunits,
                                                                                                 unit_base);
-  nz_rec_kernel<<<static_cast<unsigned>((words + 3) / 4), kBlock, 0, st>>>(row_off, head, rows, words, nz_pref, rec);
+  nz_rec_kernel<<<static_cast<unsigned>((words + 3) / 4), kBlock, 0, st>>>(row_off, head, rows, words, nz_pref, rec,
+                                                                           loc);
 }
 
 void hub_count(const uint32_t* deg, int64_t n, uint32_t min_deg, eid_t* cnt, hipStream_t st) {

@@ -611,7 +611,14 @@ PYBIND11_MODULE(_dbfs_native, m) {
                              [](const DeviceGraph& g) {
                                return py::make_tuple(g.ingest().byte_begin, g.ingest().byte_end, g.ingest().edges);
                              })
-      .def("degrees_of", &DeviceGraph::degrees_of);
+      .def("degrees_of", &DeviceGraph::degrees_of)
+      // debug: ShardView::nz_loc of the non-empty rows (empty without packed records)
+      .def("debug_nz_loc", [](const DeviceGraph& g) {
+        const std::vector<uint16_t> v = g.debug_nz_loc();
+        py::array_t<uint16_t> out(static_cast<py::ssize_t>(v.size()));
+        if (!v.empty()) std::memcpy(out.mutable_data(), v.data(), v.size() * sizeof(uint16_t));
+        return out;
+      });
 
   py::class_<RunResult>(m, "RunResult")
       .def_readonly("source", &RunResult::source)

@@ -77,6 +77,18 @@ def main():
             extra.append(f"L2 read req {c['TCP_TCC_READ_REQ_sum'] / us / 1e3:.1f} G/s")
         if c.get("SQ_INSTS_VMEM_RD"):
             extra.append(f"vmem-rd wave-insts {c['SQ_INSTS_VMEM_RD'] / us / 1e3:.2f} G/s")
+        # instruction side: wave-instructions issued per wave, and the share of the
+        # resident waves' cycles (SQ_WAVE_CYCLES, quad-cycles like the ACTIVE counters)
+        # a unit was executing; x waves per SIMD = that unit's busy share of the kernel
+        if c.get("SQ_WAVES"):
+            per_wave = [f"{k[9:].lower()} {c[k] / c['SQ_WAVES']:.0f}" for k in
+                        ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS") if c.get(k)]
+            if per_wave:
+                extra.append("insts per wave: " + " ".join(per_wave))
+        if c.get("SQ_WAVE_CYCLES"):
+            for k, label in (("SQ_ACTIVE_INST_VALU", "valu-active"), ("SQ_ACTIVE_INST_SCA", "scalar-active")):
+                if c.get(k):
+                    extra.append(f"{label} {100 * c[k] / c['SQ_WAVE_CYCLES']:.1f}% of wave-cycles")
         print("         " + "; ".join(extra))
 
 
