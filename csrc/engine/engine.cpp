@@ -335,6 +335,14 @@ std::vector<uint16_t> DeviceGraph::debug_nz_loc() const {
   return out;
 }
 
+void DeviceGraph::debug_drop_records() {
+  be_->synchronize();
+  nz_rec_ = DBuf<NzRec>();
+  nz_loc_ = DBuf<uint16_t>();
+  unit_base_ = DBuf<eid_t>();
+  rec_all_ = false;
+}
+
 std::vector<eid_t> DeviceGraph::degrees_of(const std::vector<int64_t>& local_rows) const {
   std::vector<eid_t> out;
   out.reserve(local_rows.size());

@@ -41,9 +41,10 @@ struct ShardView {
   const eid_t* row_off = nullptr;  // rows + 1 (local)
   const vid_t* col = nullptr;      // row_off[rows]
   int64_t n = 0, lo = 0, rows = 0, nnz = 0;
-  // Optional per-row copy of the first neighbour (col[row_off[r]]; any value
-  // for empty rows), laid out per vertex so a wave's 64 first probes are one
-  // coalesced 256-B load instead of 64 scattered col[] lines.
+  // Per-row copy of the first neighbour (col[row_off[r]]; any value for empty
+  // rows), laid out per vertex so a wave's 64 first probes are one coalesced
+  // 256-B load instead of 64 scattered col[] lines.  Every DeviceGraph builds
+  // it; bu_step requires it.
   const vid_t* head = nullptr;
   // Hub-encoded heads (nhubs > 0): the nhubs highest-degree vertices of the
   // whole graph get compact indices; head[r] = kHubFlag | index when the row's
@@ -54,11 +55,13 @@ struct ShardView {
   // Hub-encoded copy of col (same layout; hub neighbours as kHubFlag | index),
   // read by bottom-up so that probes of hub neighbours hit LDS too.
   const vid_t* hub_col = nullptr;
-  // Optional non-empty-row view (Graph500 RMAT: about half the vertices have
-  // no edges): nz_pref[w] = number of non-empty rows before bitmap word w,
-  // nz_row_off / nz_head = row_off / head of the non-empty rows only (dense,
-  // so a bottom-up wave touches half the cache lines).  Row k of the view is
-  // [nz_row_off[k], nz_row_off[k + 1]).
+  // Non-empty-row view, built with the heads and required by bu_step: the
+  // bottom-up kernels take every row's bounds and head from it or from the
+  // records below, never from row_off / col (Graph500 RMAT: about half the
+  // vertices have no edges).  nz_pref[w] = number of non-empty rows before
+  // bitmap word w, nz_row_off / nz_head = row_off / head of the non-empty rows
+  // only (dense, so a bottom-up wave touches half the cache lines).  Row k of
+  // the view is [nz_row_off[k], nz_row_off[k + 1]).
   const eid_t* nz_pref = nullptr;
   const eid_t* nz_row_off = nullptr;
   const vid_t* nz_head = nullptr;
@@ -748,7 +751,8 @@ constexpr int kFusedGroups = kMaxFusedGrid / kFusedGroup;
 
 struct BuArgs {
   ShardView g;
-  // Zero-degree / padding bits of the owned slice (needed with g.nz_pref).
+  // Zero-degree / padding bits of the owned slice (required: a vertex's row in
+  // the non-empty-row view is found by its rank among the non-zero-degree ones).
   const word_t* zdeg = nullptr;
   // Hub frontier bits (g.nhubs bits, from hub_gather), staged in LDS.
   const word_t* hub_front = nullptr;
@@ -764,6 +768,7 @@ struct BuArgs {
   bool follow_up = false;            // the previous level was bottom-up too (launch shape)
   int whole_units = 0;               // hub kernel, compacted: 64 words per wave (1), 16 (-1), by shard size (0)
   int small_waves = 0;               // ... split units: 4 words per wave on a first level (1), never (-1), by shard size (0)
+  // (follow_up, whole_units and small_waves shape shards with packed records; without them: 16 words per wave, queued scans)
   int64_t* unit_cnt = nullptr;
   int64_t* unit_deg = nullptr;
   const LevelCtrl* ctrl = nullptr;   // device loop: runs only when ctrl->dir == 'B'

@@ -63,6 +63,10 @@ class DeviceGraph {
   // Debug / tests: host copy of ShardView::nz_loc, one entry per non-empty
   // row (empty when the shard has no packed records).
   std::vector<uint16_t> debug_nz_loc() const;
+  // Debug / tests: release the packed row records (nz_rec, nz_loc, unit_base)
+  // as if a unit spanned 2^32 edges -- bottom-up then reads the non-empty-row
+  // view and no level is hub-cut.  Call it on every rank, before the first run.
+  void debug_drop_records();
   // Reorder every row hub-first (neighbour degree descending); collective over
   // `comm` (all ranks need every vertex's degree).  One-time preprocessing.
   // With `hubs`, the (up to kMaxHubs) highest-degree vertices of the graph are
@@ -141,7 +145,9 @@ struct EngineOptions {
   // rows per lane; RMAT-26 1240 -> 1259 GTEPS, 8 and 32 worse)
   int bu_lane_limit = 16;
   // Bottom-up waves take a whole 64-word unit (1), 16 words (-1), or by shard
-  // size (0: whole units when they fill every resident wave slot).
+  // size (0: whole units when they fill every resident wave slot).  Like
+  // bu_small_waves, a shape choice of shards with packed row records: a shard
+  // without them always runs 16 words per wave.
   int bu_whole_units = 0;
   // ... units split over waves (small shards): a first bottom-up level at 4
   // words per wave instead of 16 (1), never (-1), when 16 would leave wave

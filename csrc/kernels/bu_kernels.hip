@@ -69,13 +69,7 @@ constexpr int kCutLevels = 1, kCutClaims = 2;  // hub-cut variants (bu_hub_kerne
 constexpr int kBuQueue = 64;
 // Threshold of the record-order walk (bu_wave_compact): taken by a unit with
 // at least kRecWalkNum / kRecWalkDen of its non-empty rows unvisited.
-#ifndef DBFS_REC_WALK_NUM
-#define DBFS_REC_WALK_NUM 1
-#endif
-#ifndef DBFS_REC_WALK_DEN
-#define DBFS_REC_WALK_DEN 2
-#endif
-constexpr int kRecWalkNum = DBFS_REC_WALK_NUM, kRecWalkDen = DBFS_REC_WALK_DEN;
+constexpr int kRecWalkNum = 1, kRecWalkDen = 2;
 static_assert(kBuQueue <= kWave, "one queued row per lane per flush");
 
 #ifdef DBFS_BU_STATS
@@ -294,14 +288,11 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  const eid_t* __restrict__ ro = a.g.row_off;
-  const vid_t* __restrict__ col = a.g.col;
   const word_t* __restrict__ fr = a.frontier;
-  const vid_t* __restrict__ head = a.g.head;
-  const eid_t* __restrict__ nz_ro = (head && a.g.nz_pref && a.zdeg) ? a.g.nz_row_off : nullptr;
-  // packed records: the unit's base offset, span and end of its non-empty
-  // rows are wave-uniform (one unit per wave range)
-  // (kRec: the launcher checked that the view and its records exist)
+  // Row bounds and heads: the packed records (kRec) or the non-empty-row view
+  // (bu_step checked them).  Records: the unit's base offset, span and end of
+  // its non-empty rows are wave-uniform (one unit per wave range)
+  const eid_t* __restrict__ nz_ro = a.g.nz_row_off;
   const NzRec* __restrict__ nz_rec = kRec ? a.g.nz_rec : nullptr;
   eid_t u_base = 0;
   uint32_t u_span = 0;
@@ -348,27 +339,20 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
     }
     if (idx < total) {
       loc = j * 64 + bit;
-      if (kRec || nz_ro) {
-        // dense non-empty-row view: rank = non-empty rows before the word +
-        // those below this bit (the word's prefix and zero-degree mask are
-        // L1-resident: every lane of the wave reads one of <= 16 words)
-        const int64_t k = a.g.nz_pref[w0 + j] + __popcll(~a.zdeg[w0 + j] & ((1ull << bit) - 1ull));
-        if constexpr (kRec) {
-          const NzRec r = nz_rec[k];
-          const uint32_t end = k + 1 < u_nzend ? nz_rec[k + 1].off : u_span;
-          rs = u_base + r.off;
-          len = end - r.off;
-          u = r.head;
-        } else {
-          rs = nz_ro[k];
-          len = static_cast<uint32_t>(nz_ro[k + 1] - rs);
-          u = a.g.nz_head[k];
-        }
+      // dense non-empty-row view: rank = non-empty rows before the word +
+      // those below this bit (the word's prefix and zero-degree mask are
+      // L1-resident: every lane of the wave reads one of <= 16 words)
+      const int64_t k = a.g.nz_pref[w0 + j] + __popcll(~a.zdeg[w0 + j] & ((1ull << bit) - 1ull));
+      if constexpr (kRec) {
+        const NzRec r = nz_rec[k];
+        const uint32_t end = k + 1 < u_nzend ? nz_rec[k + 1].off : u_span;
+        rs = u_base + r.off;
+        len = end - r.off;
+        u = r.head;
       } else {
-        const int64_t v = w0 * 64 + loc;
-        rs = ro[v];
-        len = static_cast<uint32_t>(ro[v + 1] - rs);
-        if (head) u = head[v];
+        rs = nz_ro[k];
+        len = static_cast<uint32_t>(nz_ro[k + 1] - rs);
+        u = a.g.nz_head[k];
       }
     }
   };
@@ -397,7 +381,8 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
   vid_t n_u = 0;
   if (!rec_walk) {
     fetch(0, n_loc, n_rs, n_len, n_u);
-    if (!head) n_u = n_len ? col[n_rs] : 0u;
+    // (a scheduling fence, no instruction: without it the whole-unit variants spill 12-24 B)
+    __builtin_amdgcn_sched_barrier(0);
   }
   int cnt32 = 0;
   // deferred row scans (kQueue): base = the unit's first row offset
@@ -411,13 +396,9 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
     if constexpr (kRec) {
       q_base = u_base;  // (every row of the unit starts at or after it; span < 2^32)
       q_span_ok = true;
-    } else if (nz_ro) {
+    } else {
       q_base = nz_ro[a.g.nz_pref[w0]];
       q_span_ok = nz_ro[a.g.nz_pref[wend]] - q_base < (eid_t(1) << 32);
-    } else {
-      const int64_t vend = min(wend * 64, a.g.rows);
-      q_base = ro[w0 * 64];
-      q_span_ok = ro[vend] - q_base < (eid_t(1) << 32);
     }
   }
   auto settle = [&](bool f, int l, eid_t r0, eid_t r1) {
@@ -544,9 +525,7 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
       const eid_t rs = n_rs, e = n_rs + n_len;
       const vid_t u0 = n_u;
       fetch(b + 1, n_loc, n_rs, n_len, n_u);  // in flight during this batch's probes
-      step(loc, rs, e, u0, [&]() {
-        if (!head) n_u = n_len ? col[n_rs] : 0u;
-      });
+      step(loc, rs, e, u0, []() {});
     }
   }
   if constexpr (kQueue > 0) {
@@ -656,6 +635,20 @@ __device__ __forceinline__ void bu_post_words(const BuArgs& a, int64_t w0, int n
   push_frontier_word(a.push, a.push_rank, a.push_nranks, w0 + lane, a.new_frontier[w0 + lane]);
 }
 
+// XCD-aware unit walk: workgroup b takes the slot (b % 8) * (G / 8) + b / 8 of
+// the grid-stride walk, so each XCD (workgroups dispatch round-robin over the
+// 8) scans one contiguous eighth of every round's units.  Only when every
+// round is full (units a multiple of G x per): a partial last round remapped
+// would sit on the first few XCDs only.  Decided once, before the walk (a
+// per-round choice costs registers).  A/B: profiles/r6_xcd_remap_ab.txt.
+__device__ __forceinline__ int64_t bu_block(int64_t nunits, int per) {
+  const uint32_t g = gridDim.x, b = blockIdx.x;
+  if (g % 8 == 0 && nunits % (static_cast<int64_t>(g) * per) == 0)
+    return static_cast<int64_t>(b % 8) * (g / 8) + b / 8;
+  return b;
+}
+
+// (kQ, kRec: bu_wave_compact's kQueue, kRec.  bu_shape chooses the variant.)
 // kEnd: the level's end folded in (BuArgs::end; several ranks only -- its
 // code costs the one-rank kernels their spill-free 64 registers).
 // kCut: the hub-cut variant (first bottom-up level of a run of them),
@@ -665,28 +658,6 @@ __device__ __forceinline__ void bu_post_words(const BuArgs& a, int64_t w0, int n
 // kWW: words per wave when units are split over waves (!kWhole): 16, or 4 for
 // shards too small to fill the chip at 16 (a soc-LiveJournal1-sized graph's
 // 1184 units at 16 words per wave are 4736 waves, 18 per CU against 32 slots).
-// XCD-aware unit walk: workgroup b takes the slot (b % 8) * (G / 8) + b / 8 of
-// the grid-stride walk, so each XCD (workgroups dispatch round-robin over the
-// 8) scans one contiguous eighth of every round's units -- its row records,
-// level bytes and edge runs in its own L2 and translation caches -- instead
-// of every eighth group of them.  Only when every round is full (units a
-// multiple of G x per, as on the power-of-two RMAT shards): a partial last
-// round remapped would sit on the first few XCDs only (a small shard's one
-// partial round measured -10 % on the soc-LiveJournal1-sized graph).  Decided
-// once, before the walk: a per-round choice cost the fused-finish variants
-// 2-4 VGPRs and the cut variant a 12-B spill.
-// Same-box A/B on RMAT-26 (profiles/r6_xcd_remap_ab.txt): flat to +0.5 %
-// (the scan's traffic is streaming rows plus random frontier probes, which
-// no mapping localises); DBFS_NO_XCD_REMAP restores the plain order.
-__device__ __forceinline__ int64_t bu_block(int64_t nunits, int per) {
-  const uint32_t g = gridDim.x, b = blockIdx.x;
-#ifndef DBFS_NO_XCD_REMAP
-  if (g % 8 == 0 && nunits % (static_cast<int64_t>(g) * per) == 0)
-    return static_cast<int64_t>(b % 8) * (g / 8) + b / 8;
-#endif
-  return b;
-}
-
 template <bool kWhole, int kThreads = kHubBuThreads, int kQ = kBuQueue, bool kRec = false, bool kEnd = false,
           int kCut = 0, bool kPost = false, int kWW = kWaveWords>
 __global__ __launch_bounds__(kThreads, 2 * kThreads / 256) void bu_hub_kernel(BuArgs a) {
@@ -1023,6 +994,107 @@ static void bu_stats_report(hipStream_t st) {
 }
 #endif
 
+namespace {
+// ---- the hub kernels' variant table ----------------------------------------------
+// The launch shape of a level, decided once for the plain and the hub-cut
+// level (bu_shape); bu_dispatch turns it into bu_hub_kernel's arguments:
+//   shard with packed records (kRec)    kWhole  kQ        kWW  kCut   kEnd, kPost
+//     whole units                        true    kBuQueue  16   0/1/2  a.end, a.push
+//     split, 16 words per wave           false   kBuQueue  16   0/1/2  a.end, a.push
+//     ... after a bottom-up level        false   0         16   0      a.end, a.push
+//     split, 4 words per wave            false   kBuQueue  4    0      a.end, a.push
+//     ... a hub-cut level                false   kBuQueue  4    1/2    neither (else 16 words)
+//   shard without records                false   kBuQueue  16   0      a.end, a.push
+struct BuShape {
+  bool rec = false;      // rows from the packed records (else the non-empty-row view)
+  int cut = 0;           // hub-cut level: kCutLevels / kCutClaims
+  bool whole = false;    // a whole 64-word unit per wave, else ...
+  int ww = kWaveWords;   // ... units split over waves: words per wave, 16 or 4
+  int queue = kBuQueue;  // deferred row-scan queue entries per wave (0: rows scanned in place)
+  unsigned grid = 1;
+};
+
+BuShape bu_shape(const BuArgs& a) {
+  BuShape s;
+  const int64_t nunits = (a.words + kUnitWords - 1) / kUnitWords;
+  const int64_t cap = 2 * static_cast<int64_t>(device_cus());  // persistent workgroups, two per CU
+  constexpr int kSplitUnits = kHubBuThreads / kUnitThreads;    // units per workgroup at 16 words per wave
+  s.rec = a.g.nz_rec && a.g.unit_base;
+  // a hub-cut level (a first bottom-up level: the engine only asks for it
+  // there): the cut variant alone, which scans plain when the device says no
+  s.cut = a.cut_edges > 0 ? (a.cut_claim ? kCutClaims : kCutLevels) : 0;
+  if (!s.rec) {
+    // no records (a unit spanning 2^32 edges): the one form correctness needs,
+    // whatever whole_units, small_waves and follow_up ask for
+    s.grid = grid_for(nunits, kSplitUnits, cap);
+    return s;
+  }
+  // a whole 64-word unit per wave when the shard has enough units to fill
+  // every resident wave slot (one GPU); small shards (many ranks) keep 16
+  // words per wave for parallelism.  (1024-thread workgroups for every level:
+  // a level after another one ran in 768-thread ones while that variant
+  // needed 80 VGPRs; at 60-65, 1024 measured the late-switch second level
+  // 188-191 -> 160 us, RMAT-26 +2.4 %, profiles/r6_follow_1024_ab.txt)
+  const int64_t slots = cap * (kHubBuThreads / kWave);
+  s.whole = a.whole_units > 0 || (a.whole_units == 0 && nunits >= slots);
+  // shards too small to fill the wave slots at 16 words per wave: 4 (one
+  // unit per workgroup) for a first bottom-up level -- measured, the
+  // soc-LiveJournal1-sized graph's first level 420 -> 295 us (do mode
+  // 116 -> 146 GTEPS), RMAT-22's 45 -> 36 us; later levels, with few
+  // unvisited vertices left, ran slower that way (21 -> 26 us) and keep 16
+  const bool small = !s.whole && !a.follow_up &&
+                     (a.small_waves > 0 || (a.small_waves == 0 && nunits * (kUnitWords / kWaveWords) < slots));
+  // (the hub-cut level too: at 16 words that graph's first level ran do mode
+  // 154 -> 120 GTEPS -- but only without folded end and push, whose cut
+  // variants exist at 16 words alone)
+  s.ww = small && (s.cut == 0 || (!a.end.active && !a.push)) ? 4 : kWaveWords;
+  // split units after a bottom-up level scan rows in place, every other form defers
+  // them (a hub-cut level without the queue: late-switch levels 460-535 -> 505-560 us)
+  s.queue = !s.whole && a.follow_up ? 0 : kBuQueue;
+  // (by `small` itself: a cut level kept at 16 words has its workgroup per unit too)
+  s.grid = grid_for(nunits, s.whole ? kHubBuThreads / kWave : (small ? 1 : kSplitUnits), cap);
+  return s;
+}
+
+// f(std::true_type) or f(std::false_type): a run-time flag as a template argument.
+template <class F>
+void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// One form of the table, kEnd and kPost from the arguments (a folded level
+// end is compiled only into the kEnd variants).
+template <bool kWhole, int kQ, bool kRec, int kCut, int kWW>
+void bu_launch(const BuArgs& a, unsigned grid, hipStream_t st) {
+  if constexpr (kCut != 0 && kWW != kWaveWords) {
+    bu_hub_kernel<kWhole, kHubBuThreads, kQ, kRec, false, kCut, false, kWW><<<grid, kHubBuThreads, 0, st>>>(a);
+  } else {
+    with_bool(a.end.active, [&](auto end) {
+      with_bool(a.push != nullptr, [&](auto post) {
+        bu_hub_kernel<kWhole, kHubBuThreads, kQ, kRec, decltype(end)::value, kCut, decltype(post)::value, kWW>
+            <<<grid, kHubBuThreads, 0, st>>>(a);
+      });
+    });
+  }
+}
+
+void bu_dispatch(const BuArgs& a, const BuShape& s, hipStream_t st) {
+  if (!s.rec) return bu_launch<false, kBuQueue, false, 0, kWaveWords>(a, s.grid, st);
+  auto forms = [&](auto cut) {
+    constexpr int kCut = decltype(cut)::value;
+    if (s.whole) bu_launch<true, kBuQueue, true, kCut, kWaveWords>(a, s.grid, st);
+    else if (s.ww != kWaveWords) bu_launch<false, kBuQueue, true, kCut, 4>(a, s.grid, st);
+    else if (s.queue > 0) bu_launch<false, kBuQueue, true, kCut, kWaveWords>(a, s.grid, st);
+    else if constexpr (kCut == 0) bu_launch<false, 0, true, 0, kWaveWords>(a, s.grid, st);
+  };
+  if (s.cut == kCutClaims) forms(std::integral_constant<int, kCutClaims>{});
+  else if (s.cut == kCutLevels) forms(std::integral_constant<int, kCutLevels>{});
+  else forms(std::integral_constant<int, 0>{});
+}
+
+}  // namespace
+
 void bu_step(const BuArgs& a, hipStream_t st) {
 #ifdef DBFS_BU_STATS
   struct Report {
@@ -1031,33 +1103,16 @@ void bu_step(const BuArgs& a, hipStream_t st) {
   } report{st};
 #endif
   if (a.words <= 0) return;
+  // (rows come from the records or the view alone; every DeviceGraph builds them)
+  DBFS_CHECK(a.g.head, "bu_step: ShardView::head missing");
+  DBFS_CHECK(a.g.nz_pref, "bu_step: ShardView::nz_pref missing");
+  DBFS_CHECK(a.g.nz_row_off, "bu_step: ShardView::nz_row_off missing");
+  DBFS_CHECK(a.g.nz_head, "bu_step: ShardView::nz_head missing");
+  DBFS_CHECK(a.zdeg, "bu_step: BuArgs::zdeg missing");
   DBFS_CHECK((a.g.nhubs > 0 && a.hub_front) || !a.push, "bu_step: pushed words need the hub kernels");
   if (a.g.nhubs > 0 && a.hub_front) {
-    const int64_t nunits = (a.words + kUnitWords - 1) / kUnitWords;
-    // a whole 64-word unit per wave when the shard has enough units to fill
-    // every resident wave slot (one GPU); small shards (many ranks) keep 16
-    // words per wave for parallelism
-    const int64_t slots = 2 * static_cast<int64_t>(device_cus()) * (kHubBuThreads / kWave);
-    const bool whole = a.whole_units > 0 || (a.whole_units == 0 && nunits >= slots);
-    // whole units in 1024-thread workgroups for every bottom-up level: a
-    // level after another one (few unvisited vertices left, most of them
-    // scanning rows) ran in 768-thread ones while that variant needed 80
-    // VGPRs; at 60-65 now, 1024 threads measured the late-switch second
-    // level 188-191 -> 160 us, RMAT-26 +2.4 % (held-out +1.7 %) on two boxes
-    // (profiles/r6_follow_1024_ab.txt)
-    const int threads = kHubBuThreads;
-    // shards too small to fill the wave slots at 16 words per wave: 4 (one
-    // unit per workgroup) for a first bottom-up level -- measured, the
-    // soc-LiveJournal1-sized graph's first level 420 -> 295 us (do mode
-    // 116 -> 146 GTEPS), RMAT-22's 45 -> 36 us; later levels, with few
-    // unvisited vertices left, ran slower that way (21 -> 26 us) and keep 16
-    const bool small = !whole && !a.follow_up &&
-                       (a.small_waves > 0 || (a.small_waves == 0 && nunits * (kUnitWords / kWaveWords) < slots));
-    const unsigned grid = grid_for(nunits, whole ? threads / kWave : (small ? 1 : kHubBuThreads / kUnitThreads),
-                                   2 * device_cus());
-    // packed row records (compile-time path: the view's fallback costs registers)
-    const bool rec = a.g.nz_rec && a.g.unit_base && a.g.nz_pref && a.g.nz_row_off && a.zdeg && a.g.head;
-    if (a.fuse_scan && grid > static_cast<unsigned>(kMaxFusedGrid)) {
+    const BuShape s = bu_shape(a);
+    if (a.fuse_scan && s.grid > static_cast<unsigned>(kMaxFusedGrid)) {
       DBFS_CHECK(!a.end.active, "bu_step: a folded level end needs the fused finish");
       // (more workgroups than totals slots: finish in a kernel of its own)
       BuArgs b = a;
@@ -1066,66 +1121,9 @@ void bu_step(const BuArgs& a, hipStream_t st) {
       totals_finish(a.scan, st);
       return;
     }
-    // (every hub kernel runs the fused finish itself; a folded level end is
-    // compiled only into the kEnd variants)
-#define DBFS_BU_LAUNCH_WW(W, T, Q, R, WW)                                                                \
-  do {                                                                                                   \
-    if (a.end.active && a.push) bu_hub_kernel<W, T, Q, R, true, 0, true, WW><<<grid, T, 0, st>>>(a);     \
-    else if (a.end.active) bu_hub_kernel<W, T, Q, R, true, 0, false, WW><<<grid, T, 0, st>>>(a);         \
-    else if (a.push) bu_hub_kernel<W, T, Q, R, false, 0, true, WW><<<grid, T, 0, st>>>(a);               \
-    else bu_hub_kernel<W, T, Q, R, false, 0, false, WW><<<grid, T, 0, st>>>(a);                          \
-  } while (0)
-#define DBFS_BU_LAUNCH(W, T, Q, R)                  \
-  do {                                              \
-    if (small) DBFS_BU_LAUNCH_WW(W, T, Q, R, 4);     \
-    else DBFS_BU_LAUNCH_WW(W, T, Q, R, kWaveWords);  \
-  } while (0)
-    if (a.cut_edges > 0) {
-      // a hub-cut level (a first bottom-up level: the engine only asks for
-      // it there): the cut variant alone, which scans plain when the device
-      // decision says no
-      DBFS_CHECK(rec && !a.follow_up && a.cut_flag && (a.level8 || (a.cut_claim && a.level)) && a.g.hub_bits,
-                 "bu_step: hub-cut level without packed records / flag / claim bytes");
-      // (with the deferred row queue: without it, scans in place, the late-switch
-      // levels measured 460-535 -> 505-560 us)
-      constexpr int kCutQ = kBuQueue;
-#define DBFS_CUT_LAUNCH(W, C)                                                                                   \
-  do {                                                                                                        \
-    if (a.end.active && a.push) bu_hub_kernel<W, kHubBuThreads, kCutQ, true, true, C, true><<<grid, kHubBuThreads, 0, st>>>(a); \
-    else if (a.end.active) bu_hub_kernel<W, kHubBuThreads, kCutQ, true, true, C><<<grid, kHubBuThreads, 0, st>>>(a); \
-    else if (a.push) bu_hub_kernel<W, kHubBuThreads, kCutQ, true, false, C, true><<<grid, kHubBuThreads, 0, st>>>(a); \
-    else bu_hub_kernel<W, kHubBuThreads, kCutQ, true, false, C><<<grid, kHubBuThreads, 0, st>>>(a);          \
-  } while (0)
-      // (a small shard's first level -- 4 words per wave, one unit per
-      // workgroup, as the plain launch below: the cut variant scans plain when
-      // the decision says no, and the soc-LiveJournal1-sized graph's first
-      // level then ran at 16 words per wave, do mode 154 -> 120 GTEPS)
-      const bool small4 = small && !a.end.active && !a.push;
-#define DBFS_CUT_LAUNCH4(C) bu_hub_kernel<false, kHubBuThreads, kCutQ, true, false, C, 0, 4><<<grid, kHubBuThreads, 0, st>>>(a)
-      if (a.cut_claim) {
-        if (whole) DBFS_CUT_LAUNCH(true, kCutClaims);
-        else if (small4) DBFS_CUT_LAUNCH4(kCutClaims);
-        else DBFS_CUT_LAUNCH(false, kCutClaims);
-      } else {
-        if (whole) DBFS_CUT_LAUNCH(true, kCutLevels);
-        else if (small4) DBFS_CUT_LAUNCH4(kCutLevels);
-        else DBFS_CUT_LAUNCH(false, kCutLevels);
-      }
-#undef DBFS_CUT_LAUNCH4
-#undef DBFS_CUT_LAUNCH
-      return;
-    }
-    if (whole) {
-      if (rec) DBFS_BU_LAUNCH_WW(true, kHubBuThreads, kBuQueue, true, kWaveWords);
-      else DBFS_BU_LAUNCH_WW(true, kHubBuThreads, kBuQueue, false, kWaveWords);
-      return;
-    }
-    if (a.follow_up && rec) DBFS_BU_LAUNCH(false, kHubBuThreads, 0, true);
-    else if (a.follow_up) DBFS_BU_LAUNCH(false, kHubBuThreads, 0, false);
-    else if (rec) DBFS_BU_LAUNCH(false, kHubBuThreads, kBuQueue, true);
-    else DBFS_BU_LAUNCH(false, kHubBuThreads, kBuQueue, false);
-#undef DBFS_BU_LAUNCH
-#undef DBFS_BU_LAUNCH_WW
+    DBFS_CHECK(s.cut == 0 || (s.rec && !a.follow_up && a.cut_flag && (a.level8 || (a.cut_claim && a.level)) && a.g.hub_bits),
+               "bu_step: hub-cut level without packed records / flag / claim bytes");
+    bu_dispatch(a, s, st);
     return;
   }
   DBFS_CHECK(!a.end.active, "bu_step: a folded level end needs the hub kernels' fused finish");

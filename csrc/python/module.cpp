@@ -618,7 +618,9 @@ PYBIND11_MODULE(_dbfs_native, m) {
         py::array_t<uint16_t> out(static_cast<py::ssize_t>(v.size()));
         if (!v.empty()) std::memcpy(out.mutable_data(), v.data(), v.size() * sizeof(uint16_t));
         return out;
-      });
+      })
+      // debug: release the packed row records (every rank, before the first run)
+      .def("debug_drop_records", &DeviceGraph::debug_drop_records);
 
   py::class_<RunResult>(m, "RunResult")
       .def_readonly("source", &RunResult::source)
