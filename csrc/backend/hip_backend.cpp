@@ -68,6 +68,10 @@ class HipBackend final : public Backend {
     return "hip:" + std::to_string(dev_) + " (" + arch_ + ", " + std::to_string(cus_) + " CUs)";
   }
   int device_id() const override { return dev_; }
+  int compute_units() override {
+    on();
+    return kern::device_cus();
+  }
   double wall_clock_khz() const override { return clock_khz_; }
   void* stream_handle() override { return st_; }
   void* comm_stream_handle() override { return forked_ ? side_ : st_; }

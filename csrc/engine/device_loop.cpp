@@ -842,7 +842,14 @@ void DeviceLoop::emit_dense(Chain& c) {
     ta.new_level = L + 1;
     tu.level_direct = e_.level8_.data();
     tu.narrow_base = e_.narrow_base_;
-    if (ta.td_hub_vis) {
+    // Hub marks become level bytes (hub_apply), which only the direct form's
+    // update reads back; the device picks the form by the level's edges.  So
+    // marks only when every level the hub filter can run on (>= td_hub_edges
+    // edges) is a direct one (>= byte_edges_); else unvisited hubs are decoded
+    // and claimed like any other target, in either form.  (Marked in a bitmap
+    // level, a hub got its level byte but never its visited and frontier
+    // bits: found again later, at a deeper level.)
+    if (ta.td_hub_vis && bytes_ok_ && byte_edges_ <= opt_.td_hub_edges) {
       if (!e_.td_hub_mark_.data()) {
         e_.td_hub_mark_ = DBuf<uint8_t>(be_, static_cast<size_t>(kTdMaxHubs));
         be_.memset_async(e_.td_hub_mark_.data(), 0, e_.td_hub_mark_.bytes());

@@ -820,6 +820,10 @@ InitRunArgs Engine::init_args(int64_t source, word_t* seed_frontier, LevelCtrl* 
 
 RunResult Engine::run_bitmap(int64_t source) {
   alloc_bitmap_state();
+  // The host loop leaves bits in both frontier slices (a bottom-up level keeps
+  // its input, the last level its output): only a traversal through DeviceLoop
+  // may promise the next one zeroed slices.
+  frontier_clean_ = false;
   TraceRange trace_run(std::string("bfs.run mode=") + mode_name(opt_.mode) + " src=" + std::to_string(source));
   const int P = part_.nranks;
   const int me = comm_.rank();

@@ -86,9 +86,11 @@ struct ShardView {
   const vid_t* td_col = nullptr;
   const vid_t* td_hub_vertex = nullptr;
   int64_t td_nhubs = 0;
-  // One rank with hubs: bit v set when vertex v is a hub (the hubs are every
+  // Hubs present: bit v set when global vertex v is a hub (the hubs are every
   // vertex of degree >= the hub threshold, so a hub-first row's hubs are a
-  // prefix of it).  Read by the hub-cut bottom-up level (BuArgs::cut_edges).
+  // prefix of it).  The array covers every rank's slice (global words: an
+  // owned word w is read at cut_word_off + w).  Read by the hub-cut bottom-up
+  // level (BuArgs::cut_edges), on one rank and on several.
   const word_t* hub_bits = nullptr;
   // Degree of every hub (nhubs entries; several ranks: a hub's row lives on
   // its owner, so the hub-cut decision sums these instead of row lengths).
@@ -139,6 +141,11 @@ constexpr int kScanChunk = 1024;
 // At most this many units are prefix-scanned by a fused finish's last
 // workgroup (UpdateArgs::fold_scan): 32 per thread of a 256-thread workgroup.
 constexpr int kFoldScanUnits = 8192;
+// A shard of fewer units than this: the frontier update and the compaction
+// run a unit per workgroup, 16 words per wave (update_unit_split,
+// compact_split) -- 4x the waves, a quarter of the dependent row_off steps
+// each; from this many units on, a unit per wave.
+constexpr int64_t kUpdateSplitUnits = 4096;
 // Top-down expansion handles kTdEdgesPerBlock frontier edges per workgroup.
 constexpr int kTdThreads = 256;
 constexpr int kTdItems = 8;
@@ -1008,6 +1015,8 @@ class Backend {
   virtual DeviceKind kind() const = 0;
   virtual std::string name() const = 0;
   virtual int device_id() const { return -1; }
+  // Compute units the launchers size their grids by (0: not a GPU).
+  virtual int compute_units() { return 0; }
   virtual void* stream_handle() { return nullptr; }
   // Communication stream.  Collectives are enqueued on comm_stream_handle():
   // the compute stream itself, unless a side region is open.  fork_side()

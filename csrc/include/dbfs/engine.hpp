@@ -477,6 +477,7 @@ class Engine {
   const EngineOptions& options() const { return opt_; }
   void set_options(const EngineOptions& o) {
     opt_ = o;
+    frontier_clean_ = false;  // (the next traversal may take another path: it clears its frontier itself)
   }
 
  private:

@@ -904,18 +904,13 @@ void publish_stats(const int64_t* stats, StatsMailbox* mb, int64_t seq, hipStrea
   publish_stats_kernel<<<1, 64, 0, st>>>(stats, mb, seq);
 }
 
-// A graph of fewer units than kSplitUnits: a unit per workgroup, 16 words per
-// wave (update_unit_split, compact_split) -- 4x the waves, a quarter of the
-// dependent row_off steps each.
-constexpr int64_t kSplitUnits = 4096;
-
 void update_frontier(const UpdateArgs& a, hipStream_t st) {
   DBFS_CHECK(!a.end.active || (a.fuse_scan && a.ctrl && a.scan.stats), "update: a folded level end needs the fused finish");
   if (a.words <= 0) return;
   const int64_t nunits = (a.words + kUnitWords - 1) / kUnitWords;
   DBFS_CHECK(!a.fold_scan || (a.fuse_scan && a.scan.nunits == nunits && nunits <= kFoldScanUnits),
              "update: fold_scan needs the fused finish over at most kFoldScanUnits units");
-  const bool split = nunits < kSplitUnits;
+  const bool split = nunits < kUpdateSplitUnits;
   const int64_t per = split ? kUnitWords : kUnitWords * kUnitsPerBlock;
   // fused finish: at most kMaxFusedGrid / 8 workgroups striding over the units
   // with one ticket; up to kMaxFusedGrid with the two-level ticket
@@ -943,7 +938,7 @@ void scan_units(const ScanArgs& a, hipStream_t st) {
 void compact_frontier(const CompactArgs& a, hipStream_t st) {
   if (a.words <= 0) return;
   const int64_t nunits = (a.words + kUnitWords - 1) / kUnitWords;
-  if (nunits < kSplitUnits) compact_kernel<true><<<grid_for(a.words, kUnitWords), kBlock, 0, st>>>(a);
+  if (nunits < kUpdateSplitUnits) compact_kernel<true><<<grid_for(a.words, kUnitWords), kBlock, 0, st>>>(a);
   else compact_kernel<false><<<grid_for(a.words, kUnitWords * kUnitsPerBlock), kBlock, 0, st>>>(a);
 }
 

@@ -16,8 +16,6 @@
 namespace dbfs {
 namespace kern {
 
-// Compute units of the current device (bfs_kernels.hip).
-int device_cus();
 // Checked build: the first violation recorded by the top-down / bottom-up
 // kernel files (cleared); bfs_kernels.hip's take_check_error reads all three.
 unsigned long long take_check_td();

@@ -8,6 +8,9 @@
 namespace dbfs {
 namespace kern {
 
+// Compute units of the current device (bfs_kernels.hip).
+int device_cus();
+
 // bfs_kernels.hip, td_kernels.hip, bu_kernels.hip
 void fill_level(lvl_t* level, int64_t n, lvl_t value, hipStream_t st);
 // zero `bytes` at p with 16-B stores (false: p or bytes not 16-B aligned)

@@ -114,6 +114,10 @@ PYBIND11_MODULE(_dbfs_native, m) {
   m.attr("TD_EDGES_PER_BLOCK") = py::int_(kTdEdgesPerBlock);
   m.attr("UNIT_VERTICES") = py::int_(kUnitVertices);
   m.attr("MAX_HUBS") = py::int_(kMaxHubs);
+  m.attr("SCAN_CHUNK") = py::int_(kScanChunk);
+  m.attr("FOLD_SCAN_UNITS") = py::int_(kFoldScanUnits);
+  m.attr("MAX_FUSED_GRID") = py::int_(kMaxFusedGrid);
+  m.attr("UPDATE_SPLIT_UNITS") = py::int_(kUpdateSplitUnits);
 
   // ---- graphs ----
   py::class_<HostCSR>(m, "HostCSR")
@@ -252,6 +256,7 @@ PYBIND11_MODULE(_dbfs_native, m) {
   py::class_<Backend, std::shared_ptr<Backend>>(m, "Backend")
       .def_property_readonly("name", &Backend::name)
       .def_property_readonly("device_id", &Backend::device_id)
+      .def_property_readonly("compute_units", &Backend::compute_units)
       .def_property_readonly("device_bytes", &Backend::device_bytes)
       .def_property_readonly("peak_device_bytes", &Backend::peak_device_bytes)
       .def_property_readonly("is_gpu", [](const Backend& b) { return b.kind() == DeviceKind::HIP; })

@@ -32,10 +32,12 @@ class BFSResult:
 
     @property
     def chains(self) -> List[Any]:
-        """Device loop: every level chain enqueued, in order, as (level, form,
-        list capacity, gathered, pushed, unvisited filter, parts)
-        -- form T / S / L / B / X (mispredicted chains included); parts > 1: a
-        split top-down level (Options td_split_edges / td_split_parts)."""
+        """Device loop: every level chain enqueued, in order, as an 8-tuple
+        (level, form, list capacity, gathered, pushed, unvisited filter, parts,
+        hub cut) -- form T / S / L / B / X (mispredicted chains included);
+        parts > 1 (index 6): a split top-down level (Options td_split_edges /
+        td_split_parts); hub cut (index 7): a first bottom-up level enqueued
+        with the hub cut (Options bu_cut_edges)."""
         return list(self._native.chains) if self._native is not None else []
 
     @property

@@ -626,6 +626,30 @@ def test_td_hub_filter_gpu(gpu_runtime, mode, vis_frac):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["td", "do"])
+def test_td_hub_filter_bitmap_levels_gpu(gpu_runtime, mode):
+    """The hub filter on levels the device runs in the bitmap form
+    (td_direct_edges above the graph's edges, one-byte levels): unvisited hubs
+    are claimed in `next` like any other target -- marked for hub_apply they
+    would get a level byte the bitmap form's update never reads, and be found
+    again at a deeper level.  Exact levels and records' discovered counts."""
+    p = dbfs.rmat_params(17, 16, 21)
+    csr = dbfs.host_csr_from_params(p)
+    b = dbfs.BFS(p, gpu_runtime, mode=mode)
+    b.engine.set_option("td_hub_edges", 1)
+    b.engine.set_option("td_direct_edges", float(1 << 40))
+    b.engine.set_option("td_sparse_edges", 0)
+    for src in b.sample_roots(3, seed=3):
+        r = _check(b, csr, src)
+        exp = dbfs.cpu_bfs(csr, src)[0]
+        cnt = np.bincount(exp[exp != dbfs.UNREACHED])
+        for rec in r.levels:
+            k = rec["level"]
+            assert rec["discovered"] == (int(cnt[k + 1]) if k + 1 < cnt.size else 0), (src, k)
+        assert b.validate(src)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["td", "bu", "do"])
 def test_narrow_epochs_stale_bytes_gpu(gpu_runtime, mode):
     """Runs alternate between an RMAT component and a 62-level path (the
