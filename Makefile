@@ -23,9 +23,9 @@ LDLIBS    := -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -Wl,-rpath,
 
 HOST_SRC  := csrc/graph/io.cpp csrc/graph/csr.cpp csrc/backend/cpu_backend.cpp \
              csrc/backend/hip_backend.cpp csrc/comm/comm.cpp csrc/comm/nccl_comm.cpp \
-             csrc/comm/tcp_bootstrap.cpp csrc/comm/peer_comm.cpp csrc/comm/replay_comm.cpp csrc/engine/engine.cpp csrc/engine/device_loop.cpp csrc/graph/shard_reader.cpp
+             csrc/comm/tcp_bootstrap.cpp csrc/comm/peer_comm.cpp csrc/comm/replay_comm.cpp csrc/engine/engine.cpp csrc/engine/batch.cpp csrc/engine/device_loop.cpp csrc/graph/shard_reader.cpp
 HIP_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/graph_kernels.hip csrc/kernels/ref_kernels.hip \
-             csrc/kernels/graph_sort.hip csrc/kernels/peer_kernels.hip
+             csrc/kernels/graph_sort.hip csrc/kernels/peer_kernels.hip csrc/kernels/ms_kernels.hip
 
 HOST_OBJ  := $(patsubst csrc/%.cpp,$(BUILD)/%.o,$(HOST_SRC))
 HIP_OBJ   := $(patsubst csrc/%.hip,$(BUILD)/%.o,$(HIP_SRC))

@@ -196,6 +196,113 @@ class CpuBackend final : public Backend {
     for (int k = 0; k < 4; ++k) mb->v[k] = stats[k];
     __atomic_store_n(&mb->seq, seq, __ATOMIC_RELEASE);
   }
+  // ---- concurrent multi-source BFS (backend.hpp MsState): plain loops ----
+  static void ms_store_level(const MsState& s, int64_t row, int src, int level) {
+    if (s.lvl_bytes == 2) static_cast<uint16_t*>(s.lvl)[row * kMsSources + src] = static_cast<uint16_t>(level);
+    else static_cast<uint8_t*>(s.lvl)[row * kMsSources + src] = static_cast<uint8_t>(level);
+  }
+  static void ms_publish(const MsState& s) {
+    if (!s.mailbox) return;
+    for (int k = 0; k < kMsStats; ++k) s.mailbox->v[k] = s.stats[k];
+    __atomic_store_n(&s.mailbox->seq, s.seq, __ATOMIC_RELEASE);
+  }
+  // a vertex with new bits: levels, the next active list, the level's totals
+  static void ms_record(const MsState& s, int64_t row, word_t nw) {
+    if (!nw) return;
+    s.active_out[s.cursor[0]++] = static_cast<vid_t>(row);
+    s.stats[1] += s.g.row_off[row + 1] - s.g.row_off[row];
+    for (int b = 0; b < kMsSources; ++b) {
+      if (!((nw >> b) & 1ull)) continue;
+      s.stats[2 + b] += 1;
+      if (s.lvl) ms_store_level(s, row, b, s.level);
+    }
+  }
+  static void ms_level_end(const MsState& s) {
+    s.stats[0] = static_cast<int64_t>(s.cursor[0]);
+    s.cursor[0] = 0;
+    ms_publish(s);
+  }
+  void ms_init(const MsInitArgs& a) override {
+    const MsState& s = a.s;
+    std::fill(s.seen, s.seen + a.next_words, word_t(0));
+    std::fill(s.next, s.next + a.next_words, word_t(0));
+    std::fill(s.front, s.front + a.front_words, word_t(0));
+    if (s.lvl) std::memset(s.lvl, 0xFF, static_cast<size_t>(a.next_words) * kMsSources * s.lvl_bytes);
+    std::fill(s.stats, s.stats + kMsStats, int64_t(0));
+    for (int t = 0; t < a.k; ++t) {
+      const int64_t v = a.src[t];
+      const word_t bit = word_t(1) << t;
+      s.front[v] |= bit;
+      if (v < s.g.lo || v >= s.g.lo + s.g.rows) continue;
+      const int64_t r = v - s.g.lo;
+      if (!s.seen[r]) {
+        s.active_out[s.stats[0]++] = static_cast<vid_t>(r);
+        s.stats[1] += s.g.row_off[r + 1] - s.g.row_off[r];
+      }
+      s.seen[r] |= bit;
+      s.stats[2 + t] = 1;
+      if (s.lvl) ms_store_level(s, r, t, 0);
+    }
+    ms_publish(s);
+  }
+  void ms_pull(const MsPullArgs& a) override {
+    const MsState& s = a.s;
+    const ShardView& g = s.g;
+    std::fill(s.stats, s.stats + kMsStats, int64_t(0));
+    for (int64_t v = 0; v < g.rows; ++v) {
+      const word_t need = ~s.seen[v] & s.batch_mask;
+      word_t got = 0;
+      if (need)
+        for (eid_t e = g.row_off[v]; e < g.row_off[v + 1]; ++e) {
+          got |= s.front[g.col[e]];
+          if ((got & need) == need) break;
+        }
+      const word_t nw = got & need;
+      s.seen[v] |= nw;
+      s.next[v] = nw;
+      ms_record(s, v, nw);
+    }
+    ms_level_end(s);
+  }
+  void ms_push(const MsPushArgs& a) override {
+    const MsState& s = a.s;
+    const ShardView& g = s.g;
+    for (int64_t i = 0; i < a.clear_n; ++i) s.next[a.clear_list[i]] = 0;
+    for (int64_t i = 0; i < a.n_active; ++i) {
+      const vid_t v = a.active[i];
+      const word_t f = s.front[v];
+      s.front[v] = 0;
+      for (eid_t e = g.row_off[v]; e < g.row_off[v + 1]; ++e) {
+        const vid_t w = g.col[e];
+        const word_t m = f & ~s.seen[w];
+        if (!m) continue;
+        const word_t old = s.next[w];
+        s.next[w] = old | m;
+        if (!old) a.touched[s.cursor[1]++] = w;
+      }
+    }
+  }
+  void ms_settle(const MsSettleArgs& a) override {
+    const MsState& s = a.s;
+    std::fill(s.stats, s.stats + kMsStats, int64_t(0));
+    const int64_t n = std::min<int64_t>(static_cast<int64_t>(s.cursor[1]), a.max_touched);
+    for (int64_t i = 0; i < n; ++i) {
+      const vid_t w = a.touched[i];
+      const word_t nw = s.next[w] & ~s.seen[w];
+      s.seen[w] |= nw;
+      s.next[w] = nw;
+      ms_record(s, w, nw);
+    }
+    s.cursor[1] = 0;
+    ms_level_end(s);
+  }
+  void ms_degree_sums(const MsDegreeArgs& a) override {
+    for (int64_t v = 0; v < a.g.rows; ++v) {
+      const int64_t deg = a.g.row_off[v + 1] - a.g.row_off[v];
+      word_t sv = deg ? a.seen[v] : 0;
+      for (; sv; sv &= sv - 1) a.deg_sum[__builtin_ctzll(sv)] += deg;
+    }
+  }
   void* alloc_mapped(size_t bytes, void** dptr) override {
     void* h = std::calloc(1, std::max<size_t>(bytes, 1));
     DBFS_CHECK(h != nullptr, "host allocation failed");

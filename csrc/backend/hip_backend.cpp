@@ -259,6 +259,20 @@ class HipBackend final : public Backend {
     kern::widen_levels(in, out, n, base, st_);
     chk();
   }
+  void ms_init(const MsInitArgs& a) override {
+    const MsState& s = a.s;
+    memset_async(s.seen, 0, static_cast<size_t>(a.next_words) * sizeof(word_t));
+    memset_async(s.next, 0, static_cast<size_t>(a.next_words) * sizeof(word_t));
+    memset_async(s.front, 0, static_cast<size_t>(a.front_words) * sizeof(word_t));
+    if (s.lvl) memset_async(s.lvl, 0xFF, static_cast<size_t>(a.next_words) * kMsSources * s.lvl_bytes);
+    on();
+    kern::ms_init(a, st_);
+    chk();
+  }
+  void ms_pull(const MsPullArgs& a) override { on(); kern::ms_pull(a, st_); chk(); }
+  void ms_push(const MsPushArgs& a) override { on(); kern::ms_push(a, st_); chk(); }
+  void ms_settle(const MsSettleArgs& a) override { on(); kern::ms_settle(a, st_); chk(); }
+  void ms_degree_sums(const MsDegreeArgs& a) override { on(); kern::ms_degree_sums(a, st_); chk(); }
   void td_expand(const TdArgs& a) override { on(); kern::td_expand(a, st_); chk(); }
   void td_binned(const BinArgs& a) override { on(); kern::td_binned(a, st_); chk(); }
   void pack_bytes(const PackArgs& a) override { on(); kern::pack_bytes(a, st_); chk(); }

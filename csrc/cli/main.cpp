@@ -57,6 +57,8 @@ struct Args {
   int64_t uni_n = 0, uni_m = 0;
   uint64_t seed = 1;
   int roots = 0;
+  bool batch = false;                 // --roots K: the K roots as one concurrent traversal (Engine::run_batch)
+  std::string batch_dir = "auto";
   bool oracle = true;
   bool validate = false;
   std::string levels_out;
@@ -78,6 +80,7 @@ struct Args {
                "       --mode ref|td|bu|do|simple|scan  --alpha A --beta B --bu-lane-limit K\n"
                "       --rmat SCALE[:EF] | --uniform N:M   --seed S\n"
                "       --roots K (random sources, GTEPS summary)  --no-oracle  --validate\n"
+               "       --batch (the K roots concurrently, 64 per pass)  --batch-direction auto|push|pull|alternate\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only)\n"
@@ -115,6 +118,8 @@ Args parse(int argc, char** argv) {
       a.uni_m = std::stoll(v.substr(c + 1));
     } else if (s == "--seed") a.seed = std::stoull(next());
     else if (s == "--roots") a.roots = std::stoi(next());
+    else if (s == "--batch") a.batch = true;
+    else if (s == "--batch-direction") a.batch_dir = next();
     else if (s == "--no-oracle") a.oracle = false;
     else if (s == "--validate") a.validate = true;
     else if (s == "--levels-out") a.levels_out = next();
@@ -582,7 +587,45 @@ int main(int argc, char** argv) {
       std::printf("%s\n", json_run(res[0], gname, n, m_in, P, a.mode.c_str(), bname, ranks[0].comm->name(), ingest_json).c_str());
 
     // ---- optional K random roots (Graph500-style GTEPS) ----
-    if (a.roots > 0) {
+    if (a.roots > 0 && a.batch) {
+      // ---- the K roots as one concurrent traversal ----
+      const std::vector<int64_t> roots = sample_roots(a, part, ranks, multiproc, wrank);
+      const bool check = a.oracle && have_host;  // (the same on every rank of this process)
+      const BatchDirection bdir = parse_batch_direction(a.batch_dir);
+      std::vector<BatchResult> bres(static_cast<size_t>(nlocal));
+      std::vector<lvl_t> blv;
+      if (!roots.empty())
+        run_ranks(ranks, [&](int i, RankCtx& rc) {
+          bres[i] = rc.engine->run_batch(roots, bdir, a.oracle);
+          if (!a.oracle) return;
+          std::vector<lvl_t> lv = rc.engine->gather_batch_levels();
+          if (i == 0) blv = std::move(lv);
+        }, vgroup.get());
+      if (leader && check && !roots.empty()) {
+        for (size_t k = 0; k < roots.size(); ++k) {
+          const std::vector<lvl_t> exp = cpu_bfs(full, roots[k]).level;
+          const lvl_t* row = blv.data() + k * static_cast<size_t>(n);
+          for (int64_t i = 0; i < n; ++i) {
+            if (row[i] != exp[i]) {
+              std::printf("root %lld: %lld %d %d\n", static_cast<long long>(roots[k]), static_cast<long long>(i), row[i],
+                          exp[i]);
+              std::printf("Wrong output!\n");
+              return 1;
+            }
+          }
+        }
+        if (!a.quiet) std::printf("Output OK!\n\n");
+      }
+      if (leader && !roots.empty()) {
+        const BatchResult& b = bres[0];
+        std::printf("batch roots %zu passes %d ms %.3f aggregate GTEPS %.3f\n", roots.size(), b.passes, b.ms, b.gteps);
+        if (a.json)
+          std::printf("{\"graph\":\"%s\",\"n\":%lld,\"ranks\":%d,\"batch\":true,\"roots\":%zu,\"passes\":%d,\"ms\":%.6f,"
+                      "\"gteps\":%.6f,\"wide_levels\":%s}\n",
+                      gname.c_str(), static_cast<long long>(n), P, roots.size(), b.passes, b.ms, b.gteps,
+                      b.wide_levels ? "true" : "false");
+      }
+    } else if (a.roots > 0) {
       const std::vector<int64_t> roots = sample_roots(a, part, ranks, multiproc, wrank);
       double inv_sum = 0, ms_sum = 0;
       int64_t e_sum = 0;

@@ -1,0 +1,345 @@
+// Concurrent multi-source BFS (Engine::run_batch): up to 64 sources per pass,
+// one bit per source in a 64-bit word per vertex ("The More the Merrier",
+// Then et al., VLDB 2015).  A host loop: per level one kernel (pull) or two
+// (push + settle) and one totals read -- through a host-mapped mailbox on one
+// rank, after the all-gather / all-reduce on several.
+//
+// Buffers of a level (one rank): `front` holds the frontier words (non-zero
+// exactly at the active list's vertices), `next` receives the new bits, then
+// the two swap.  A push zeroes the front words it consumes, so the buffer
+// comes back clean; a pull writes every word of `next` and leaves its
+// frontier in place -- the push after a pull first zeroes those words through
+// that level's active list (MsPushArgs::clear_list).  No level clears a whole
+// array.
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <utility>
+
+#include "dbfs/engine.hpp"
+#include "spin.hpp"
+
+namespace dbfs {
+
+namespace {
+
+// Direction rule (Auto, one rank).  A push level costs a scattered `seen`
+// probe and often a returning atomic per edge of the active vertices; a pull
+// level reads the rows of every vertex that still misses a source, at most
+// all directed edges E of the graph.  Push while the active vertices' degree
+// sum is below E / kMsPullEnter; once pulling, stay until it is below
+// E / kMsPushBack.  Chosen from the per-level push and pull times of the same
+// levels on RMAT-20..26, a uniform graph and a road grid (one MI355X,
+// profiles/ms_bfs_ab.txt): levels at E / 8.6 .. E / 33.7 run 1.5-4x faster
+// pushed, one at E / 3.8 2x faster pulled; on the way back a pull stays ahead
+// down to about E / 300 (16 was tried for kMsPushBack and pushed a level too
+// early).
+constexpr int64_t kMsPullEnter = 8;
+constexpr int64_t kMsPushBack = 64;
+
+// Deepest level a level matrix entry holds (its all-ones value reads unreached).
+constexpr int kMsMaxLevel8 = kMsUnreached8 - 1, kMsMaxLevel16 = kMsUnreached16 - 1;
+
+}  // namespace
+
+BatchDirection parse_batch_direction(const std::string& s) {
+  if (s == "auto") return BatchDirection::Auto;
+  if (s == "push") return BatchDirection::Push;
+  if (s == "pull") return BatchDirection::Pull;
+  if (s == "alternate") return BatchDirection::Alternate;
+  throw Error("batch direction must be auto, push, pull or alternate: '" + s + "'");
+}
+
+int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out) {
+  const int P = part_.nranks;
+  const int64_t W = part_.part;  // owned vertices, padded: every rank's slice of `front`
+  const int64_t front_words = P > 1 ? W * P : W;
+  if (!ms_) ms_ = std::make_unique<MsBuffers>();
+  MsBuffers& b = *ms_;
+  if (b.seen.size() == 0) {
+    b.seen = DBuf<word_t>(be_, static_cast<size_t>(W));
+    b.next = DBuf<word_t>(be_, static_cast<size_t>(W));
+    b.front = DBuf<word_t>(be_, static_cast<size_t>(front_words));
+    b.list[0] = DBuf<vid_t>(be_, static_cast<size_t>(W));
+    b.list[1] = DBuf<vid_t>(be_, static_cast<size_t>(W));
+    b.touched = DBuf<vid_t>(be_, static_cast<size_t>(W));
+    // (a push queues rows of more than 1024 entries: at most nnz / 1024 of them)
+    b.long_v = DBuf<vid_t>(be_, static_cast<size_t>(g_.nnz() / 1024 + 1));
+    b.long_f = DBuf<word_t>(be_, b.long_v.size());
+    b.cursor = DBuf<unsigned long long>(be_, 3);
+    b.tot = DBuf<int64_t>(be_, static_cast<size_t>(kMsMaxGrid) * kMsStats);
+    b.stats = DBuf<int64_t>(be_, kMsStats);
+    b.deg_sum = DBuf<int64_t>(be_, kMsSources);
+    b.ticket = DBuf<unsigned>(be_, 1);
+    be_.memset_async(b.cursor.data(), 0, b.cursor.bytes());
+    be_.memset_async(b.ticket.data(), 0, b.ticket.bytes());
+    if (P == 1) {
+      void* dptr = nullptr;
+      b.mb_host = static_cast<MsMailbox*>(be_.alloc_mapped(sizeof(MsMailbox), &dptr));
+      b.mb_dev = static_cast<MsMailbox*>(dptr);
+    }
+  }
+  if (lvl_bytes != b.lvl_bytes) {
+    b.lvl.reset();
+    b.lvl_bytes = 0;
+    if (lvl_bytes) {
+      b.lvl = DBuf<uint8_t>(be_, static_cast<size_t>(W) * kMsSources * lvl_bytes);
+      b.lvl_bytes = lvl_bytes;
+    }
+  }
+  const int max_level = lvl_bytes == 1 ? kMsMaxLevel8 : kMsMaxLevel16;
+
+  MsState s;
+  s.g = g_.view();
+  s.seen = b.seen.data();
+  s.front = b.front.data();
+  s.next = b.next.data();
+  s.lvl = lvl_bytes ? b.lvl.data() : nullptr;
+  s.lvl_bytes = lvl_bytes;
+  s.batch_mask = k == kMsSources ? ~word_t(0) : (word_t(1) << k) - 1;
+  s.cursor = b.cursor.data();
+  s.tot = b.tot.data();
+  s.ticket = b.ticket.data();
+  s.stats = b.stats.data();
+  s.mailbox = b.mb_dev;
+
+  // the level's totals on the host (several ranks: global sums)
+  int64_t h[kMsStats];
+  auto read_totals = [&](bool reduce) {
+    if (P == 1) {
+      MsMailbox* mb = b.mb_host;
+      const int64_t seq = b.seq;
+      spin_until(be_, [&] { return __atomic_load_n(&mb->seq, __ATOMIC_ACQUIRE) == seq; },
+                 "batch totals mailbox: stream drained without the stamp");
+      for (int i = 0; i < kMsStats; ++i) h[i] = __atomic_load_n(&mb->v[i], __ATOMIC_RELAXED);
+      return;
+    }
+    if (reduce) comm_.allreduce_sum_i64(b.stats.data(), kMsStats);
+    be_.to_host(h, b.stats.data(), sizeof(h));
+  };
+
+  int cur = 0;  // list[cur]: the active vertices of the level about to run
+  MsInitArgs ia;
+  ia.k = k;
+  std::copy(src, src + k, ia.src);
+  ia.next_words = W;
+  ia.front_words = front_words;
+  s.level = 0;
+  s.active_out = b.list[cur].data();
+  s.seq = ++b.seq;
+  ia.s = s;
+  be_.ms_init(ia);
+  read_totals(true);
+  int64_t local_active = h[0];  // (several ranks: the global count; only one rank pushes)
+
+  const size_t first = out.discovered.size() - static_cast<size_t>(k);  // this pass's sources in `out`
+  const size_t first_level_rec = out.levels.size();
+  auto note_discovered = [&](int level) {
+    for (int t = 0; t < k; ++t) {
+      auto& d = out.discovered[first + t];
+      if (h[2 + t]) {
+        d.resize(static_cast<size_t>(level) + 1, 0);
+        d[level] = h[2 + t];
+      }
+    }
+  };
+  note_discovered(0);
+
+  bool pulling = false, prev_pull = false;
+  int64_t prev_local_active = 0;
+  for (int level = 1; h[0] > 0; ++level) {
+    if (level > max_level) {
+      // (identical on every rank: the totals are global)
+      DBFS_CHECK(lvl_bytes == 1, "run_batch: a traversal reached 65535 levels");
+      for (int t = 0; t < k; ++t) out.discovered[first + t].clear();
+      out.levels.resize(first_level_rec);
+      return 1;
+    }
+    const int64_t n_a = h[0], m_a = h[1];
+    bool pull = true;
+    if (P == 1) {
+      switch (dir) {
+        case BatchDirection::Push: pull = false; break;
+        case BatchDirection::Pull: pull = true; break;
+        case BatchDirection::Alternate: pull = ((level - 1) & 1) != 0; break;
+        case BatchDirection::Auto:
+          pulling = pulling ? m_a * kMsPushBack >= total_directed_ : m_a * kMsPullEnter > total_directed_;
+          pull = pulling;
+          break;
+      }
+    }
+    BatchLevelRecord rec;
+    rec.pass = pass;
+    rec.level = level - 1;
+    rec.form = pull ? 'L' : 'P';
+    rec.active = n_a;
+    rec.edges = m_a;
+    out.levels.push_back(rec);
+    const auto lt0 = std::chrono::steady_clock::now();
+
+    s.level = level;
+    s.active_out = b.list[cur ^ 1].data();
+    s.seq = ++b.seq;
+    if (pull) {
+      MsPullArgs pa;
+      pa.s = s;
+      be_.ms_pull(pa);
+      if (P > 1) {
+        comm_.allgather_allreduce(s.next, s.front, static_cast<size_t>(W) * sizeof(word_t), b.stats.data(), kMsStats);
+      } else {
+        std::swap(s.front, s.next);
+      }
+    } else {
+      MsPushArgs pa;
+      pa.s = s;
+      pa.active = b.list[cur].data();
+      pa.n_active = local_active;
+      pa.touched = b.touched.data();
+      pa.active_edges = m_a;
+      pa.long_v = b.long_v.data();
+      pa.long_f = b.long_f.data();
+      pa.long_cap = static_cast<int64_t>(b.long_v.size());
+      if (prev_pull) {
+        pa.clear_list = b.list[cur ^ 1].data();
+        pa.clear_n = prev_local_active;
+      }
+      be_.ms_push(pa);
+      MsSettleArgs sa;
+      sa.s = s;
+      sa.touched = b.touched.data();
+      sa.max_touched = std::min<int64_t>(g_.rows(), m_a);
+      be_.ms_settle(sa);
+      std::swap(s.front, s.next);
+    }
+    prev_pull = pull;
+    prev_local_active = local_active;
+    cur ^= 1;
+    read_totals(false);
+    local_active = h[0];
+    out.levels.back().ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - lt0).count();
+    note_discovered(level);
+  }
+
+  // end pass: per-source degree sums of the reached
+  be_.memset_async(b.deg_sum.data(), 0, b.deg_sum.bytes());
+  MsDegreeArgs da;
+  da.g = s.g;
+  da.seen = s.seen;
+  da.deg_sum = b.deg_sum.data();
+  be_.ms_degree_sums(da);
+  if (P > 1) comm_.allreduce_sum_i64(b.deg_sum.data(), kMsSources);
+  int64_t deg[kMsSources];
+  be_.to_host(deg, b.deg_sum.data(), sizeof(deg));
+  for (int t = 0; t < k; ++t) {
+    const auto& d = out.discovered[first + t];
+    int64_t reached = 0, dist = 0;
+    for (size_t l = 0; l < d.size(); ++l) {
+      reached += d[l];
+      dist += static_cast<int64_t>(l) * d[l];
+    }
+    out.reached[first + t] = reached;
+    out.dist_sum[first + t] = dist;
+    out.depth[first + t] = static_cast<int>(d.size());
+    out.edges[first + t] = deg[t] / 2;
+  }
+  return 0;
+}
+
+BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirection dir, bool keep_levels) {
+  DBFS_CHECK(!opt_.directed, "run_batch: directed graphs are not supported (the pull form searches in-edges)");
+  DBFS_CHECK(!sources.empty(), "run_batch: no sources");
+  for (int64_t v : sources) DBFS_CHECK(v >= 0 && v < part_.n, "run_batch: source vertex out of range");
+  DBFS_CHECK(part_.nranks == 1 || dir != BatchDirection::Push,
+             "run_batch: the push form runs on one rank only (several ranks: every level is a pull)");
+  const int64_t k = static_cast<int64_t>(sources.size());
+  BatchResult out;
+  out.sources = sources;
+  out.passes = static_cast<int>(div_up(k, kMsSources));
+  batch_k_ = -1;
+  batch_pending_first_ = -1;
+  batch_levels_.clear();
+  if (keep_levels) batch_levels_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), kUnreached);
+  double ms = 0.0;
+  for (int pass = 0; pass < out.passes; ++pass) {
+    const int64_t first = static_cast<int64_t>(pass) * kMsSources;
+    const int kp = static_cast<int>(std::min<int64_t>(kMsSources, k - first));
+    if (batch_pending_first_ >= 0) {  // (outside the timed window)
+      collect_batch_levels(batch_pending_first_, batch_pending_k_);
+      batch_pending_first_ = -1;
+    }
+    out.discovered.resize(static_cast<size_t>(first + kp));
+    out.reached.resize(static_cast<size_t>(first + kp), 0);
+    out.edges.resize(static_cast<size_t>(first + kp), 0);
+    out.dist_sum.resize(static_cast<size_t>(first + kp), 0);
+    out.depth.resize(static_cast<size_t>(first + kp), 0);
+    comm_.barrier();
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool wide = ms_ && ms_->wide;
+    int lvl_bytes = keep_levels ? (wide ? 2 : 1) : 0;
+    if (run_batch_pass(sources.data() + first, kp, pass, dir, lvl_bytes, out) != 0) {
+      // deeper than one-byte levels hold (or, without a level matrix, than
+      // 16-bit ones would): once more with 16-bit levels, both runs timed
+      ms_->wide = true;
+      lvl_bytes = 2;
+      const int again = run_batch_pass(sources.data() + first, kp, pass, dir, lvl_bytes, out);
+      DBFS_CHECK(again == 0, "run_batch: the 16-bit rerun overflowed");
+    }
+    if (lvl_bytes == 2) out.wide_levels = true;
+    be_.synchronize();
+    const auto t1 = std::chrono::steady_clock::now();
+    ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    if (keep_levels) {
+      batch_pending_first_ = first;
+      batch_pending_k_ = kp;
+    }
+  }
+  out.ms = comm_.max_host(ms);
+  int64_t edges = 0;
+  for (int64_t e : out.edges) edges += e;
+  out.gteps = out.ms > 0 ? static_cast<double>(edges) / (out.ms * 1e6) : 0.0;
+  if (keep_levels) batch_k_ = k;
+  return out;
+}
+
+// The level matrix of the pass just run -> rows [first, first + k) of batch_levels_.
+void Engine::collect_batch_levels(int64_t first, int k) {
+  const int P = part_.nranks;
+  const int64_t W = part_.part, n = part_.n;
+  MsBuffers& b = *ms_;
+  const size_t bytes = static_cast<size_t>(W) * kMsSources * b.lvl_bytes;
+  std::vector<uint8_t> hb(bytes * P);
+  if (P > 1) {
+    DBuf<uint8_t> all(be_, bytes * P);
+    comm_.allgather(b.lvl.data(), all.data(), bytes);
+    be_.to_host(hb.data(), all.data(), hb.size());
+  } else {
+    be_.to_host(hb.data(), b.lvl.data(), bytes);
+  }
+  // (slices are W vertices each, so global vertex v is row v of the gathered matrix)
+  for (int t = 0; t < k; ++t) {
+    lvl_t* row = batch_levels_.data() + static_cast<size_t>(first + t) * static_cast<size_t>(n);
+    if (b.lvl_bytes == 2) {
+      const uint16_t* m = reinterpret_cast<const uint16_t*>(hb.data());
+      for (int64_t v = 0; v < n; ++v) {
+        const uint16_t x = m[v * kMsSources + t];
+        row[v] = x == kMsUnreached16 ? kUnreached : static_cast<lvl_t>(x);
+      }
+    } else {
+      for (int64_t v = 0; v < n; ++v) {
+        const uint8_t x = hb[static_cast<size_t>(v) * kMsSources + t];
+        row[v] = x == kMsUnreached8 ? kUnreached : static_cast<lvl_t>(x);
+      }
+    }
+  }
+}
+
+std::vector<lvl_t> Engine::gather_batch_levels() {
+  DBFS_CHECK(batch_k_ > 0, "gather_batch_levels: no batch has run with keep_levels");
+  if (batch_pending_first_ >= 0) {
+    collect_batch_levels(batch_pending_first_, batch_pending_k_);
+    batch_pending_first_ = -1;
+  }
+  return batch_levels_;
+}
+
+}  // namespace dbfs

@@ -531,6 +531,7 @@ Engine::~Engine() {
   if (mailbox_host_) be_.free_mapped(mailbox_host_);
   for (auto& seg : rec_segs_) be_.free_mapped(seg.first);
   if (stats_mb_host_) be_.free_mapped(stats_mb_host_);
+  if (ms_ && ms_->mb_host) be_.free_mapped(ms_->mb_host);
 }
 
 

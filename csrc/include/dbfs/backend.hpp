@@ -1007,6 +1007,104 @@ struct ParentArgs {
   int64_t* parent = nullptr;            // rows (owned slice)
 };
 
+// ---- concurrent multi-source BFS (Engine::run_batch) -------------------------
+// One batch is at most kMsSources sources; source s is bit s of a 64-bit word
+// per vertex.  seen / next are indexed by owned row, front by global vertex
+// (one rank: the same).  A level is either one ms_pull, or ms_push + ms_settle
+// (one rank only); both leave the level's totals in stats[0..kMsStats) and,
+// with a mailbox, stamp them there for the spinning host.
+constexpr int kMsSources = 64;
+// stats: [0] vertices with new bits (the next level's active list), [1] their
+// degree sum, [2 + s] vertices source s discovered
+constexpr int kMsStats = 2 + kMsSources;
+// workgroups of an ms kernel at most (they stride over their work; one totals
+// slot of kMsStats entries each)
+constexpr int kMsMaxGrid = 1024;
+// level matrix entries that read unreached (u8 / u16 levels)
+constexpr int kMsUnreached8 = 0xFF, kMsUnreached16 = 0xFFFF;
+
+// Host-mapped totals of a batch level (as StatsMailbox: values first, then seq).
+struct MsMailbox {
+  int64_t seq = 0;
+  int64_t v[kMsStats] = {};
+};
+
+// What every ms kernel shares.
+struct MsState {
+  ShardView g;
+  word_t* seen = nullptr;   // owned rows
+  word_t* front = nullptr;  // this level's frontier words, by global vertex
+  word_t* next = nullptr;   // owned rows: the new bits of this level
+  // level matrix (optional): row v holds the kMsSources levels of owned vertex
+  // v, lvl_bytes (1 or 2) each; 0: none kept
+  void* lvl = nullptr;
+  int lvl_bytes = 0;
+  word_t batch_mask = 0;    // bit s set: source s is part of the batch
+  int level = 0;            // the level new vertices get
+  vid_t* active_out = nullptr;           // owned rows with new bits (local ids), unordered
+  // [0] active_out entries, [1] touched entries, [2] queued long rows of a
+  // push; zero between levels
+  unsigned long long* cursor = nullptr;
+  int64_t* tot = nullptr;                // kMsMaxGrid x kMsStats per-workgroup totals
+  unsigned* ticket = nullptr;            // zero between launches
+  int64_t* stats = nullptr;              // kMsStats
+  MsMailbox* mailbox = nullptr;          // device pointer; nullptr: stats only
+  int64_t seq = 0;
+};
+
+// Clears seen / next (next_words) / front (front_words) and the level matrix,
+// then seeds the batch: bit s of seen / front of src[s], level 0, the distinct
+// owned sources as the first active list, their totals in stats.
+struct MsInitArgs {
+  MsState s;
+  int k = 0;
+  int64_t src[kMsSources] = {};  // global vertex ids (duplicates allowed)
+  int64_t next_words = 0, front_words = 0;
+};
+
+// Dense form: every owned vertex with need = ~seen & batch_mask != 0 ORs the
+// front words of its row until need is covered; new = acc & need goes to
+// seen, next (every owned word is written, zero included) and the level matrix.
+struct MsPullArgs {
+  MsState s;
+  int lane_limit = 32;  // neighbours a lane reads itself before its row goes to the wave
+};
+
+// Sparse form (one rank): for every active vertex v and neighbour w,
+// m = front[v] & ~seen[w] is ORed into next[w]; the first toucher of w appends
+// it to `touched`.  front[v] is zeroed by the lane that read it.
+struct MsPushArgs {
+  MsState s;
+  const vid_t* active = nullptr;
+  int64_t n_active = 0;
+  vid_t* touched = nullptr;
+  // words of `next` to zero first (the level before was a pull, which read
+  // this buffer as its frontier): that level's active list
+  const vid_t* clear_list = nullptr;
+  int64_t clear_n = 0;
+  // degree sum of the active vertices, and (HIP) the queue of the rows too
+  // long for one wave: vertex and frontier word, long_cap entries
+  int64_t active_edges = 0;
+  vid_t* long_v = nullptr;
+  word_t* long_f = nullptr;
+  int64_t long_cap = 0;
+};
+
+// Over the touched list of the push before it (cursor[1] entries, at most
+// max_touched): new = next & ~seen, then the pull form's bookkeeping.
+struct MsSettleArgs {
+  MsState s;
+  const vid_t* touched = nullptr;
+  int64_t max_touched = 0;
+};
+
+// End pass of a batch: deg_sum[s] += degree of every owned vertex source s reached.
+struct MsDegreeArgs {
+  ShardView g;
+  const word_t* seen = nullptr;
+  int64_t* deg_sum = nullptr;  // kMsSources, zero on entry
+};
+
 // ---- backend ----------------------------------------------------------------
 
 class Backend {
@@ -1206,6 +1304,12 @@ class Backend {
   virtual void degree_moments(const ShardView& g, int64_t* out2) = 0;
   // out[i] = in[i] (narrow levels; kNarrowUnreached -> kUnreached)
   virtual void widen_levels(const uint8_t* in, lvl_t* out, int64_t n, uint8_t base) = 0;
+  // concurrent multi-source BFS (MsState)
+  virtual void ms_init(const MsInitArgs& a) = 0;
+  virtual void ms_pull(const MsPullArgs& a) = 0;
+  virtual void ms_push(const MsPushArgs& a) = 0;
+  virtual void ms_settle(const MsSettleArgs& a) = 0;
+  virtual void ms_degree_sums(const MsDegreeArgs& a) = 0;
 
  protected:
   std::function<void(double)> wait_watch_;

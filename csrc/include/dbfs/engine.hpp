@@ -446,6 +446,37 @@ struct RunResult {
   std::vector<ChainRecord> chains;  // device loop: every chain enqueued, in order
 };
 
+// Concurrent multi-source BFS (Engine::run_batch): which form a level takes.
+// Auto decides per level (one rank; several ranks: every level is a pull);
+// Alternate is push on even levels and pull on odd ones (tests: both
+// transitions on every graph).
+enum class BatchDirection { Auto, Push, Pull, Alternate };
+BatchDirection parse_batch_direction(const std::string& s);
+
+// One level of one pass: form 'P' push, 'L' pull; the active vertices it
+// expanded and the sum of their degrees (global).
+struct BatchLevelRecord {
+  int pass = 0, level = 0;
+  char form = 'L';
+  int64_t active = 0, edges = 0;
+  double ms = 0.0;  // host wall time from the level's enqueue to its totals
+};
+
+struct BatchResult {
+  std::vector<int64_t> sources;
+  double ms = 0.0;     // wall time of all passes (max over ranks)
+  double gteps = 0.0;  // sum of edges / ms
+  int passes = 0;      // ceil(k / 64)
+  // the level matrix is 16-bit: a pass (of this batch or an earlier one) was
+  // deeper than one-byte levels hold and was rerun
+  bool wide_levels = false;
+  // per source, in the order given
+  std::vector<int64_t> reached, edges, dist_sum;  // edges: degree sum of the reached / 2
+  std::vector<int> depth;                         // levels (max level + 1)
+  std::vector<std::vector<int64_t>> discovered;   // [source][level]
+  std::vector<BatchLevelRecord> levels;
+};
+
 // Fault injection for failure-detection tests (see Engine::inject_fault).
 struct FaultSpec {
   int rank = -1, level = -1;
@@ -473,6 +504,16 @@ class Engine {
   // owned slice, and the full array (all ranks participate in both).
   std::vector<int64_t> parents_local(int64_t source);
   std::vector<int64_t> gather_parents(int64_t source);
+  // Concurrent traversal from all `sources`, 64 per pass (one bit per source
+  // in a 64-bit word per vertex); collective.  The single-source state (run)
+  // is not touched.  keep_levels: the per-source levels are kept for
+  // gather_batch_levels (64 bytes per vertex on the device).
+  BatchResult run_batch(const std::vector<int64_t>& sources, BatchDirection dir = BatchDirection::Auto,
+                        bool keep_levels = true);
+  // The last batch's levels, [k][n] row-major, kUnreached where source k does
+  // not reach; collective.  Throws when the batch ran without keep_levels.
+  std::vector<lvl_t> gather_batch_levels();
+  int64_t batch_sources() const { return batch_k_; }  // of the last batch with levels (-1: none)
   int64_t global_directed_edges() const { return total_directed_; }
   const EngineOptions& options() const { return opt_; }
   void set_options(const EngineOptions& o) {
@@ -578,6 +619,30 @@ class Engine {
   StatsMailbox* stats_mb_dev_ = nullptr;
   int64_t stats_seq_ = 0;
   void read_level_stats(int64_t* host_stats);
+  // concurrent multi-source state (csrc/engine/batch.cpp), allocated by the
+  // first batch; separate from everything above
+  struct MsBuffers {
+    DBuf<word_t> seen, front, next;
+    DBuf<uint8_t> lvl;
+    int lvl_bytes = 0;  // of the allocated matrix (0: none)
+    DBuf<vid_t> list[2], touched, long_v;
+    DBuf<word_t> long_f;
+    DBuf<unsigned long long> cursor;
+    DBuf<int64_t> tot, stats, deg_sum;
+    DBuf<unsigned> ticket;
+    MsMailbox* mb_host = nullptr;
+    MsMailbox* mb_dev = nullptr;
+    int64_t seq = 0;
+    bool wide = false;  // a batch overflowed the one-byte levels: 16-bit from then on
+  };
+  std::unique_ptr<MsBuffers> ms_;
+  // 0: done; 1: deeper than the level type holds (rerun wider)
+  int run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out);
+  void collect_batch_levels(int64_t first, int k);
+  std::vector<lvl_t> batch_levels_;      // [k][n], passes collected so far
+  int64_t batch_k_ = -1;                 // sources of the last batch (-1: none, or without levels)
+  int64_t batch_pending_first_ = -1;     // last pass not collected yet: its first source ...
+  int batch_pending_k_ = 0;              // ... and size
   // reference-mode state
   bool ref_ready_ = false;
   DBuf<lvl_t> dist_;

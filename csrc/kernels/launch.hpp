@@ -60,6 +60,13 @@ void status_expand(const StatusArgs& a, hipStream_t st);
 void bitmap_or(word_t* dst, const word_t* src, int64_t words, hipStream_t st);
 void copy_pieces(const Backend::CopyPieces& c, hipStream_t st);
 
+// ms_kernels.hip (concurrent multi-source BFS; ms_init after the state's fills)
+void ms_init(const MsInitArgs& a, hipStream_t st);
+void ms_pull(const MsPullArgs& a, hipStream_t st);
+void ms_push(const MsPushArgs& a, hipStream_t st);
+void ms_settle(const MsSettleArgs& a, hipStream_t st);
+void ms_degree_sums(const MsDegreeArgs& a, hipStream_t st);
+
 // peer_kernels.hip (PeerComm: collectives through peer-mapped windows)
 constexpr int kMaxPeers = 16;
 struct PeerPushArgs {

@@ -644,6 +644,30 @@ PYBIND11_MODULE(_dbfs_native, m) {
                              })
       .def("level_dicts", &level_dicts);
 
+  py::class_<BatchResult>(m, "BatchResult")
+      .def_readonly("sources", &BatchResult::sources)
+      .def_readonly("ms", &BatchResult::ms)
+      .def_readonly("gteps", &BatchResult::gteps)
+      .def_readonly("passes", &BatchResult::passes)
+      .def_readonly("wide_levels", &BatchResult::wide_levels)
+      .def_readonly("reached", &BatchResult::reached)
+      .def_readonly("edges", &BatchResult::edges)
+      .def_readonly("depth", &BatchResult::depth)
+      .def_readonly("dist_sum", &BatchResult::dist_sum)
+      .def_readonly("discovered", &BatchResult::discovered)
+      // per level of each pass: (pass, level, form 'P' push / 'L' pull, active vertices, their edges, ms)
+      .def_property_readonly("levels",
+                             [](const BatchResult& r) {
+                               py::list out;
+                               for (const auto& l : r.levels)
+                                 out.append(py::make_tuple(l.pass, l.level, std::string(1, l.form), l.active, l.edges, l.ms));
+                               return out;
+                             })
+      .def("__repr__", [](const BatchResult& r) {
+        return "BatchResult(sources=" + std::to_string(r.sources.size()) + ", passes=" + std::to_string(r.passes) +
+               ", ms=" + std::to_string(r.ms) + ", gteps=" + std::to_string(r.gteps) + ")";
+      });
+
   py::class_<Engine, std::shared_ptr<Engine>>(m, "Engine")
       .def(py::init([](std::shared_ptr<DeviceGraph> g, std::shared_ptr<Comm> c, const std::string& mode, double alpha,
                        double beta, int bu_lane_limit, bool phase_timing, bool force_exchange) {
@@ -686,6 +710,31 @@ PYBIND11_MODULE(_dbfs_native, m) {
             return out;
           },
           py::arg("sources"))
+      .def(
+          "run_batch",
+          [](Engine& e, const std::vector<int64_t>& sources, const std::string& direction, bool levels) {
+            const BatchDirection d = parse_batch_direction(direction);
+            BatchResult r;
+            {
+              py::gil_scoped_release rel;
+              r = e.run_batch(sources, d, levels);
+            }
+            return r;
+          },
+          py::arg("sources"), py::arg("direction") = "auto", py::arg("levels") = true)
+      .def("gather_batch_levels",
+           [](Engine& e) {
+             std::vector<lvl_t> v;
+             int64_t k = 0;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_batch_levels();
+               k = e.batch_sources();
+             }
+             py::array_t<lvl_t> a = to_numpy(v);
+             a.resize({static_cast<py::ssize_t>(k), static_cast<py::ssize_t>(k ? v.size() / k : 0)});
+             return a;
+           })
       .def("levels_local",
            [](const Engine& e) {
              std::vector<lvl_t> v;

@@ -15,6 +15,7 @@ from .._native import N
 from ..parallel.runtime import Runtime, init_runtime
 
 MODES = ("ref", "td", "bu", "do", "simple", "scan")
+BATCH_DIRECTIONS = ("auto", "push", "pull", "alternate")
 
 
 class BFSResult:
@@ -56,6 +57,30 @@ class BFSResult:
             return cls(r["source"], r["ms"], r["reached"], r["edges"], r["depth"], r["gteps"],
                        levels=list(r["levels"]), mispredicts=int(r.get("mispredicts", 0)))
         return cls(r.source, r.ms, r.reached, r.edges, r.depth, r.gteps, mispredicts=r.mispredicts, native=r)
+
+
+class BatchResult:
+    """One concurrent traversal from k sources (``BFS.run_batch``), 64 sources
+    per pass.  Per source, in the order given: ``reached``, ``edges`` (degree
+    sum of the reached // 2), ``depth`` (levels), ``dist_sum`` (sum of levels
+    over the reached) and ``discovered[s][L]`` (vertices source s found at
+    level L).  ``levels``: per level of each pass a tuple (pass, level, form,
+    active vertices, their edges, host ms), form 'P' push or 'L' pull.  ``wide_levels``:
+    the levels are 16-bit (a pass deeper than 254 levels, in this batch or an
+    earlier one, was rerun)."""
+
+    __slots__ = ("sources", "ms", "gteps", "passes", "wide_levels", "reached", "edges", "depth", "dist_sum",
+                 "discovered", "levels")
+
+    def __init__(self, r: Any):
+        self.sources, self.ms, self.gteps, self.passes = list(r.sources), r.ms, r.gteps, r.passes
+        self.wide_levels = bool(r.wide_levels)
+        self.reached, self.edges, self.depth = list(r.reached), list(r.edges), list(r.depth)
+        self.dist_sum, self.discovered, self.levels = list(r.dist_sum), [list(d) for d in r.discovered], list(r.levels)
+
+    def __repr__(self) -> str:
+        return (f"BatchResult(sources={len(self.sources)}, passes={self.passes}, ms={self.ms:.4f}, "
+                f"gteps={self.gteps:.2f})")
 
 
 class BFS:
@@ -141,6 +166,23 @@ class BFS:
         return to Python between them: the host gap between two traversals is
         the engine's own).  Collective like run()."""
         return [BFSResult.from_native(r) for r in self.engine.run_many([int(s) for s in sources])]
+
+    def run_batch(self, sources, direction: str = "auto", levels: bool = True) -> BatchResult:
+        """One concurrent traversal from all ``sources`` (64 per pass, one bit
+        per source in a 64-bit word per vertex); collective like run().
+        ``direction``: "auto" picks push or pull per level (one rank; several
+        ranks always pull), "push" / "pull" / "alternate" force a form.
+        ``levels=False`` keeps no level matrix (64 bytes per vertex on the
+        device): the totals are the same, batch_levels() then raises.  The
+        single-source state of run() is left alone."""
+        if direction not in BATCH_DIRECTIONS:
+            raise ValueError(f"direction must be one of {BATCH_DIRECTIONS}")
+        return BatchResult(self.engine.run_batch([int(s) for s in sources], direction, bool(levels)))
+
+    def batch_levels(self) -> np.ndarray:
+        """Levels of the last run_batch as int32 [k, n] (UNREACHED where a
+        source does not reach); collective."""
+        return self.engine.gather_batch_levels()
 
     def levels(self) -> np.ndarray:
         """Full per-vertex level array of the last run (collective)."""
