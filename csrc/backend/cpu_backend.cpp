@@ -303,6 +303,41 @@ class CpuBackend final : public Backend {
       for (; sv; sv &= sv - 1) a.deg_sum[__builtin_ctzll(sv)] += deg;
     }
   }
+  void ms_check(const MsCheckArgs& a) override {
+    const ShardView& g = a.g;
+    const int none = a.lvl_bytes == 2 ? kMsUnreached16 : kMsUnreached8;
+    auto level = [&](int64_t v, int s) -> int {
+      const int64_t i = v * kMsSources + s;
+      return a.lvl_bytes == 2 ? static_cast<const uint16_t*>(a.lvl)[i] : static_cast<const uint8_t*>(a.lvl)[i];
+    };
+    for (int64_t r = 0; r < g.rows; ++r) {
+      const int64_t u = g.lo + r;
+      for (int s = 0; s < a.k; ++s) {
+        const int lu = level(u, s);
+        int64_t gap = 0, cross = 0;
+        uint32_t par = kMsNoParent;
+        bool has_parent = false;
+        for (eid_t e = g.row_off[r]; e < g.row_off[r + 1]; ++e) {
+          const vid_t w = g.col[e];
+          const int lw = level(w, s);
+          if (lu == none && lw == none) continue;
+          if ((lu == none) != (lw == none)) { ++cross; continue; }
+          if (lu - lw > 1 || lw - lu > 1) ++gap;
+          if (lw == lu - 1 && !has_parent) {
+            has_parent = true;
+            par = w;
+          }
+        }
+        const bool is_src = u == a.src[s];
+        if (a.out) {
+          a.out[kMsCheckCounters * s + 0] += gap;
+          a.out[kMsCheckCounters * s + 1] += cross;
+          if (is_src ? lu != 0 : (lu != none && !has_parent)) a.out[kMsCheckCounters * s + 2] += 1;
+        }
+        if (a.par) a.par[r * kMsSources + s] = is_src ? static_cast<uint32_t>(u) : par;
+      }
+    }
+  }
   void* alloc_mapped(size_t bytes, void** dptr) override {
     void* h = std::calloc(1, std::max<size_t>(bytes, 1));
     DBFS_CHECK(h != nullptr, "host allocation failed");

@@ -273,6 +273,7 @@ class HipBackend final : public Backend {
   void ms_push(const MsPushArgs& a) override { on(); kern::ms_push(a, st_); chk(); }
   void ms_settle(const MsSettleArgs& a) override { on(); kern::ms_settle(a, st_); chk(); }
   void ms_degree_sums(const MsDegreeArgs& a) override { on(); kern::ms_degree_sums(a, st_); chk(); }
+  void ms_check(const MsCheckArgs& a) override { on(); kern::ms_check(a, st_); chk(); }
   void td_expand(const TdArgs& a) override { on(); kern::td_expand(a, st_); chk(); }
   void td_binned(const BinArgs& a) override { on(); kern::td_binned(a, st_); chk(); }
   void pack_bytes(const PackArgs& a) override { on(); kern::pack_bytes(a, st_); chk(); }

@@ -81,6 +81,7 @@ struct Args {
                "       --rmat SCALE[:EF] | --uniform N:M   --seed S\n"
                "       --roots K (random sources, GTEPS summary)  --no-oracle  --validate\n"
                "       --batch (the K roots concurrently, 64 per pass)  --batch-direction auto|push|pull|alternate\n"
+               "       --batch --validate (every pass's levels checked on the device, all its sources at once)\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only)\n"
@@ -596,7 +597,8 @@ int main(int argc, char** argv) {
       std::vector<lvl_t> blv;
       if (!roots.empty())
         run_ranks(ranks, [&](int i, RankCtx& rc) {
-          bres[i] = rc.engine->run_batch(roots, bdir, a.oracle);
+          // (--validate: the device check reads the level matrix, oracle or not)
+          bres[i] = rc.engine->run_batch(roots, bdir, a.oracle || a.validate, a.validate);
           if (!a.oracle) return;
           std::vector<lvl_t> lv = rc.engine->gather_batch_levels();
           if (i == 0) blv = std::move(lv);
@@ -619,11 +621,35 @@ int main(int argc, char** argv) {
       if (leader && !roots.empty()) {
         const BatchResult& b = bres[0];
         std::printf("batch roots %zu passes %d ms %.3f aggregate GTEPS %.3f\n", roots.size(), b.passes, b.ms, b.gteps);
-        if (a.json)
+        // --validate: the device check's counts (global sums, the same on every rank)
+        size_t clean = 0;
+        long long viol[3] = {0, 0, 0};
+        if (a.validate) {
+          for (size_t k = 0; k < roots.size(); ++k) {
+            const int64_t* v = b.violations.data() + 3 * k;
+            if (!v[0] && !v[1] && !v[2]) ++clean;
+            for (int c = 0; c < 3; ++c) viol[c] += v[c];
+          }
+          std::printf("batch validation %zu/%zu sources clean gap %lld cross %lld orphan %lld\n", clean, roots.size(),
+                      viol[0], viol[1], viol[2]);
+        }
+        if (a.json) {
+          std::string extra;
+          if (a.validate) {
+            char ms[64];
+            std::snprintf(ms, sizeof(ms), "%.6f", b.check_ms);
+            extra = ",\"validated_sources\":\"" + std::to_string(clean) + "/" + std::to_string(roots.size()) +
+                    "\",\"check_ms\":" + ms;
+          }
           std::printf("{\"graph\":\"%s\",\"n\":%lld,\"ranks\":%d,\"batch\":true,\"roots\":%zu,\"passes\":%d,\"ms\":%.6f,"
-                      "\"gteps\":%.6f,\"wide_levels\":%s}\n",
+                      "\"gteps\":%.6f,\"wide_levels\":%s%s}\n",
                       gname.c_str(), static_cast<long long>(n), P, roots.size(), b.passes, b.ms, b.gteps,
-                      b.wide_levels ? "true" : "false");
+                      b.wide_levels ? "true" : "false", extra.c_str());
+        }
+        if (a.validate && clean != roots.size()) {
+          std::printf("Wrong output!\n");
+          rc_exit = 1;
+        }
       }
     } else if (a.roots > 0) {
       const std::vector<int64_t> roots = sample_roots(a, part, ranks, multiproc, wrank);

@@ -245,7 +245,10 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
   return 0;
 }
 
-BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirection dir, bool keep_levels) {
+BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirection dir, bool keep_levels, bool validate,
+                              bool keep_parents) {
+  DBFS_CHECK(keep_levels || !(validate || keep_parents),
+             "run_batch: validate and keep_parents read the level matrix (keep_levels)");
   DBFS_CHECK(!opt_.directed, "run_batch: directed graphs are not supported (the pull form searches in-edges)");
   DBFS_CHECK(!sources.empty(), "run_batch: no sources");
   for (int64_t v : sources) DBFS_CHECK(v >= 0 && v < part_.n, "run_batch: source vertex out of range");
@@ -257,9 +260,14 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirectio
   out.passes = static_cast<int>(div_up(k, kMsSources));
   batch_k_ = -1;
   batch_pending_first_ = -1;
+  batch_last_k_ = 0;
+  batch_parents_k_ = -1;
   batch_levels_.clear();
+  batch_parents_.clear();
   if (keep_levels) batch_levels_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), kUnreached);
-  double ms = 0.0;
+  if (keep_parents) batch_parents_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.part), -1);
+  if (validate) out.violations.assign(static_cast<size_t>(k) * kMsCheckCounters, 0);
+  double ms = 0.0, check_ms = 0.0;
   for (int pass = 0; pass < out.passes; ++pass) {
     const int64_t first = static_cast<int64_t>(pass) * kMsSources;
     const int kp = static_cast<int>(std::min<int64_t>(kMsSources, k - first));
@@ -291,9 +299,20 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirectio
     if (keep_levels) {
       batch_pending_first_ = first;
       batch_pending_k_ = kp;
+      batch_last_k_ = kp;
+    }
+    if (validate || keep_parents) {
+      // (after the timed window, before the next pass reuses the matrix; a
+      // pass rerun with 16-bit levels is checked here once, on the rerun's)
+      check_batch_pass(sources.data() + first, kp,
+                       validate ? out.violations.data() + static_cast<size_t>(first) * kMsCheckCounters : nullptr,
+                       keep_parents, first);
+      check_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     }
   }
   out.ms = comm_.max_host(ms);
+  if (validate || keep_parents) out.check_ms = comm_.max_host(check_ms);
+  if (keep_parents) batch_parents_k_ = k;
   int64_t edges = 0;
   for (int64_t e : out.edges) edges += e;
   out.gteps = out.ms > 0 ? static_cast<double>(edges) / (out.ms * 1e6) : 0.0;
@@ -331,6 +350,117 @@ void Engine::collect_batch_levels(int64_t first, int k) {
       }
     }
   }
+}
+
+// Backend::ms_check on the pass's matrix (several ranks: the all-gathered
+// slices, W vertices each, so global vertex v is row v -- the simple form, as
+// the rest of the several-rank batch).
+void Engine::check_batch_pass(const int64_t* src, int k, int64_t* viol, bool parents, int64_t first) {
+  const int P = part_.nranks;
+  const int64_t W = part_.part;
+  MsBuffers& b = *ms_;
+  DBFS_CHECK(b.lvl_bytes != 0, "batch check: no level matrix is resident");
+  const size_t bytes = static_cast<size_t>(W) * kMsSources * b.lvl_bytes;
+  DBuf<uint8_t> all;
+  if (P > 1) {
+    all = DBuf<uint8_t>(be_, bytes * P);
+    comm_.allgather(b.lvl.data(), all.data(), bytes);
+  }
+  MsCheckArgs ca;
+  ca.g = g_.view();
+  ca.lvl = P > 1 ? all.data() : b.lvl.data();
+  ca.lvl_bytes = b.lvl_bytes;
+  ca.lvl_rows = W * P;
+  ca.k = k;
+  std::copy(src, src + k, ca.src);
+  ca.batch_mask = k == kMsSources ? ~word_t(0) : (word_t(1) << k) - 1;
+  if (viol) {
+    if (b.check.size() == 0) b.check = DBuf<int64_t>(be_, kMsSources * kMsCheckCounters);
+    be_.memset_async(b.check.data(), 0, b.check.bytes());
+    ca.out = b.check.data();
+  }
+  if (parents) {
+    if (b.par.size() == 0) b.par = DBuf<uint32_t>(be_, static_cast<size_t>(W) * kMsSources);
+    ca.par = b.par.data();
+  }
+  be_.ms_check(ca);
+  if (viol) {
+    if (P > 1) comm_.allreduce_sum_i64(b.check.data(), kMsSources * kMsCheckCounters);
+    int64_t h[kMsSources * kMsCheckCounters];
+    be_.to_host(h, b.check.data(), sizeof(h));
+    std::copy(h, h + static_cast<size_t>(k) * kMsCheckCounters, viol);
+  }
+  if (parents) {
+    // vertex-major on the device, source-major on the host: copied and
+    // transposed kChunk rows at a time (a 16 MB host temporary, not rows x 256 B)
+    constexpr int64_t kChunk = int64_t(1) << 16;
+    const int64_t rows = g_.rows();
+    std::vector<uint32_t> hp(static_cast<size_t>(std::min(rows, kChunk)) * kMsSources);
+    int64_t* const base = batch_parents_.data() + static_cast<size_t>(first) * static_cast<size_t>(W);
+    for (int64_t r0 = 0; r0 < rows; r0 += kChunk) {
+      const int64_t nr = std::min(kChunk, rows - r0);
+      be_.to_host(hp.data(), b.par.data() + static_cast<size_t>(r0) * kMsSources,
+                  static_cast<size_t>(nr) * kMsSources * sizeof(uint32_t));
+      for (int64_t r = 0; r < nr; ++r) {
+        const uint32_t* line = hp.data() + static_cast<size_t>(r) * kMsSources;
+        for (int t = 0; t < k; ++t)
+          base[static_cast<size_t>(t) * static_cast<size_t>(W) + static_cast<size_t>(r0 + r)] =
+              line[t] == kMsNoParent ? -1 : static_cast<int64_t>(line[t]);
+      }
+    }
+  }
+  be_.synchronize();  // (a rank that copied nothing back: check_ms still ends with the work done)
+}
+
+std::vector<int64_t> Engine::validate_batch_pass(const std::vector<int64_t>& sources) {
+  DBFS_CHECK(ms_ && batch_last_k_ > 0 && ms_->lvl_bytes != 0,
+             "validate_batch_pass: no batch has run with keep_levels");
+  DBFS_CHECK(static_cast<int>(sources.size()) == batch_last_k_,
+             "validate_batch_pass: expected as many sources as the last pass had (" + std::to_string(batch_last_k_) +
+                 "), got " + std::to_string(sources.size()));
+  for (int64_t v : sources) DBFS_CHECK(v >= 0 && v < part_.n, "validate_batch_pass: source vertex out of range");
+  std::vector<int64_t> viol(sources.size() * kMsCheckCounters, 0);
+  check_batch_pass(sources.data(), batch_last_k_, viol.data(), false, 0);
+  return viol;
+}
+
+void Engine::debug_set_batch_level(int slot, int64_t vertex, int level) {
+  DBFS_CHECK(ms_ && batch_last_k_ > 0 && ms_->lvl_bytes != 0,
+             "debug_set_batch_level: no batch has run with keep_levels");
+  DBFS_CHECK(slot >= 0 && slot < kMsSources && vertex >= 0 && vertex < part_.n,
+             "debug_set_batch_level: slot or vertex out of range");
+  MsBuffers& b = *ms_;
+  const int none = b.lvl_bytes == 2 ? kMsUnreached16 : kMsUnreached8;
+  DBFS_CHECK(level < none, "debug_set_batch_level: the level does not fit the matrix");
+  const int64_t r = vertex - g_.lo();
+  if (r < 0 || r >= g_.rows()) return;  // another rank's
+  const uint16_t x = static_cast<uint16_t>(level < 0 ? none : level);  // (little-endian: the low byte first)
+  be_.to_device(b.lvl.data() + (static_cast<size_t>(r) * kMsSources + slot) * b.lvl_bytes, &x,
+                static_cast<size_t>(b.lvl_bytes));
+}
+
+std::vector<int64_t> Engine::gather_batch_parents() {
+  DBFS_CHECK(batch_parents_k_ > 0, "gather_batch_parents: no batch has run with keep_parents");
+  const int P = part_.nranks;
+  const int64_t W = part_.part, n = part_.n, k = batch_parents_k_;
+  std::vector<int64_t> out(static_cast<size_t>(k) * static_cast<size_t>(n));
+  std::vector<int64_t> all;
+  const int64_t* slices = batch_parents_.data();  // [rank][k][W]
+  if (P > 1) {
+    const size_t cnt = static_cast<size_t>(k) * static_cast<size_t>(W);
+    DBuf<int64_t> send(be_, cnt), recv(be_, cnt * P);
+    be_.to_device(send.data(), batch_parents_.data(), cnt * sizeof(int64_t));
+    comm_.allgather(send.data(), recv.data(), cnt * sizeof(int64_t));
+    all.resize(cnt * P);
+    be_.to_host(all.data(), recv.data(), all.size() * sizeof(int64_t));
+    slices = all.data();
+  }
+  for (int p = 0; p < P; ++p) {
+    const int64_t lo = static_cast<int64_t>(p) * W, cnt = std::min(W, n - lo);
+    for (int64_t t = 0; t < k && cnt > 0; ++t)
+      std::copy_n(slices + (static_cast<size_t>(p) * k + t) * W, cnt, out.data() + static_cast<size_t>(t) * n + lo);
+  }
+  return out;
 }
 
 std::vector<lvl_t> Engine::gather_batch_levels() {

@@ -1105,6 +1105,36 @@ struct MsDegreeArgs {
   int64_t* deg_sum = nullptr;  // kMsSources, zero on entry
 };
 
+// Graph500-style check of a finished pass's level matrix, all sources at once
+// (ValidateArgs' rules per source; Engine::run_batch validate / keep_parents).
+// `lvl` is the full matrix: row v holds the kMsSources levels of global vertex
+// v (one rank: the pass's own matrix; several: the all-gathered slices), all
+// ones = unreached.  Over the directed adjacency entries (u, w) of the owned
+// rows, for every source s < k:
+//   count form (out):  out[3 s + 0] += entries with both ends reached and
+//     |lvl[u][s] - lvl[w][s]| > 1 (gap), out[3 s + 1] += entries with exactly
+//     one end reached (cross), out[3 s + 2] += reached u != src[s] without a
+//     neighbour one level closer, and u == src[s] with a level other than 0
+//     (orphan);
+//   parent form (par): par[r * kMsSources + s] = the first neighbour of owned
+//     row r, in stored row order, one level closer to source s (global id);
+//     src[s] itself for u == src[s]; all ones when u is unreached (or has no
+//     such neighbour).
+// Entries of sources s >= k are neither counted nor stored.
+constexpr int kMsCheckCounters = 3;
+constexpr uint32_t kMsNoParent = 0xFFFFFFFFu;
+struct MsCheckArgs {
+  ShardView g;
+  const void* lvl = nullptr;
+  int lvl_bytes = 1;
+  int64_t lvl_rows = 0;          // rows of `lvl` (>= n: the checked build's bound on column ids)
+  int k = 0;
+  int64_t src[kMsSources] = {};  // global vertex ids
+  word_t batch_mask = 0;         // bit s set: s < k
+  int64_t* out = nullptr;        // kMsSources x kMsCheckCounters, accumulated; nullptr: no counts
+  uint32_t* par = nullptr;       // owned rows x kMsSources; nullptr: no parents
+};
+
 // ---- backend ----------------------------------------------------------------
 
 class Backend {
@@ -1310,6 +1340,7 @@ class Backend {
   virtual void ms_push(const MsPushArgs& a) = 0;
   virtual void ms_settle(const MsSettleArgs& a) = 0;
   virtual void ms_degree_sums(const MsDegreeArgs& a) = 0;
+  virtual void ms_check(const MsCheckArgs& a) = 0;
 
  protected:
   std::function<void(double)> wait_watch_;

@@ -475,6 +475,13 @@ struct BatchResult {
   std::vector<int> depth;                         // levels (max level + 1)
   std::vector<std::vector<int64_t>> discovered;   // [source][level]
   std::vector<BatchLevelRecord> levels;
+  // run_batch(validate): per source, in the order given, the device check's
+  // (depth-gap, reached-unreached, orphan) counts, [k][3] row-major, summed
+  // over ranks (all must be 0); empty when not asked for
+  std::vector<int64_t> violations;
+  // wall time of the per-pass checks (validate / keep_parents; max over
+  // ranks): after each pass's timed window, never part of `ms`
+  double check_ms = 0.0;
 };
 
 // Fault injection for failure-detection tests (see Engine::inject_fault).
@@ -508,11 +515,32 @@ class Engine {
   // in a 64-bit word per vertex); collective.  The single-source state (run)
   // is not touched.  keep_levels: the per-source levels are kept for
   // gather_batch_levels (64 bytes per vertex on the device).
+  // validate: every pass's level matrix is checked on the device against
+  // every edge, all its sources at once (Backend::ms_check; Graph500's level
+  // rules as in validate()), after the pass's timed window: BatchResult::
+  // violations, check_ms.  keep_parents: the same walk also leaves every
+  // source's parent tree for gather_batch_parents (256 bytes per owned vertex
+  // on the device during the check, k x 8 bytes per owned vertex on the host).
+  // Both need keep_levels.  Several ranks: the owned slices of the matrix are
+  // all-gathered for the check, as gather_batch_levels does.
   BatchResult run_batch(const std::vector<int64_t>& sources, BatchDirection dir = BatchDirection::Auto,
-                        bool keep_levels = true);
+                        bool keep_levels = true, bool validate = false, bool keep_parents = false);
   // The last batch's levels, [k][n] row-major, kUnreached where source k does
   // not reach; collective.  Throws when the batch ran without keep_levels.
   std::vector<lvl_t> gather_batch_levels();
+  // The last batch's parent trees, [k][n] row-major, with gather_parents'
+  // convention per source (parent[src] = src, -1 unreached); collective.
+  // Throws when the batch ran without keep_parents.
+  std::vector<int64_t> gather_batch_parents();
+  int64_t batch_parent_sources() const { return batch_parents_k_; }  // of the last batch with parents (-1: none)
+  // The count form of the check once more, on the level matrix still resident
+  // from the last pass of the last batch, against `sources` (as many as that
+  // pass had, at most 64): [k][3] as BatchResult::violations; collective.
+  std::vector<int64_t> validate_batch_pass(const std::vector<int64_t>& sources);
+  // Test hook: overwrite source slot `slot`'s level of global `vertex` in the
+  // resident level matrix (on its owner; level < 0: unreached), so a test can
+  // plant a violation for validate_batch_pass to find.
+  void debug_set_batch_level(int slot, int64_t vertex, int level);
   int64_t batch_sources() const { return batch_k_; }  // of the last batch with levels (-1: none)
   int64_t global_directed_edges() const { return total_directed_; }
   const EngineOptions& options() const { return opt_; }
@@ -634,6 +662,8 @@ class Engine {
     MsMailbox* mb_dev = nullptr;
     int64_t seq = 0;
     bool wide = false;  // a batch overflowed the one-byte levels: 16-bit from then on
+    DBuf<int64_t> check;   // MsCheckArgs::out
+    DBuf<uint32_t> par;    // MsCheckArgs::par (allocated by the first batch that keeps parents)
   };
   std::unique_ptr<MsBuffers> ms_;
   // 0: done; 1: deeper than the level type holds (rerun wider)
@@ -643,6 +673,14 @@ class Engine {
   int64_t batch_k_ = -1;                 // sources of the last batch (-1: none, or without levels)
   int64_t batch_pending_first_ = -1;     // last pass not collected yet: its first source ...
   int batch_pending_k_ = 0;              // ... and size
+  // The check of the pass just run (sources src[0..k)): counts into viol
+  // ([k][3], or nullptr), parents into rows [first, first + k) of
+  // batch_parents_ (parents set).  Blocking.
+  void check_batch_pass(const int64_t* src, int k, int64_t* viol, bool parents, int64_t first);
+  int batch_last_k_ = 0;                 // sources of the last pass whose level matrix is resident (0: none)
+  // owned slices of the parent trees, [k][part] (-1: unreached or padding)
+  std::vector<int64_t> batch_parents_;
+  int64_t batch_parents_k_ = -1;         // sources of the last batch with parents (-1: none)
   // reference-mode state
   bool ref_ready_ = false;
   DBuf<lvl_t> dist_;

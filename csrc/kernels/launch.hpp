@@ -66,6 +66,7 @@ void ms_pull(const MsPullArgs& a, hipStream_t st);
 void ms_push(const MsPushArgs& a, hipStream_t st);
 void ms_settle(const MsSettleArgs& a, hipStream_t st);
 void ms_degree_sums(const MsDegreeArgs& a, hipStream_t st);
+void ms_check(const MsCheckArgs& a, hipStream_t st);
 
 // peer_kernels.hip (PeerComm: collectives through peer-mapped windows)
 constexpr int kMaxPeers = 16;

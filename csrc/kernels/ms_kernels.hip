@@ -7,6 +7,8 @@
 //   ms_push    sparse level: the active vertices OR their frontier word into
 //              their neighbours' `next` words (returning 64-bit atomic OR)
 //   ms_settle  the touched vertices of a push level: new bits, bookkeeping
+//   ms_check   after a pass: the level matrix against every edge, all sources
+//              at once (violation counts, parent trees)
 //
 // Bookkeeping of a vertex with new bits (ms_record): the level bytes (lane s
 // stores source s's level: one partial 64-B line per vertex), one
@@ -413,6 +415,111 @@ __global__ __launch_bounds__(kMsBlock) void ms_degree_kernel(MsDegreeArgs a) {
   __syncthreads();
   if (t < kMsSources && s_sum[t])
     atomicAdd(reinterpret_cast<unsigned long long*>(a.deg_sum) + t, s_sum[t]);
+}
+
+// ms_check (backend.hpp MsCheckArgs): a wave per owned vertex u, striding over
+// the rows; lane s is source s.  Lane s holds lvl[u][s] (the vertex's line of
+// the level matrix); the wave reads the row 64 column ids per step (lane i:
+// col[e + i], coalesced), and for each of them, made wave-uniform by a
+// readlane, lane s loads lvl[w][s]: one scattered 64-B line (128 B with 16-bit
+// levels) per adjacency entry, checked for all sources at once.  The walk is
+// bound by the latency of those lines, so kMsCheckAhead of them are requested
+// before the first is consumed (the last group of a row repeats its last
+// entry's line instead of branching around the loads).  Rows are walked in
+// stored order, so the parent form's first parent is the host loops' first.
+// Workgroups at most (they stride over the rows): 2048 x 4 waves = 8192 waves, the 256 CUs x 4 SIMDs
+// x 8 waves the kernel's registers allow (profiles/ms_bfs_regs.txt) when the workgroups spread evenly
+// over the CUs; not tuned against other sizes.
+constexpr int kMsCheckGrid = 2048;
+constexpr int kMsCheckAhead = 8;
+
+template <class L, bool kCount, bool kParent>
+__global__ __launch_bounds__(kMsBlock) void ms_check_kernel(MsCheckArgs a) {
+  __shared__ unsigned long long s_cnt[kMsSources * kMsCheckCounters];
+  const ShardView& g = a.g;
+  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
+  constexpr int kNone = static_cast<int>(static_cast<L>(~static_cast<L>(0)));
+  const int t = threadIdx.x;
+  const int lane = lane_id();
+  if (kCount) {
+    if (t < kMsSources * kMsCheckCounters) s_cnt[t] = 0ull;
+    __syncthreads();
+  }
+  const bool on = (a.batch_mask >> lane) & 1ull;  // lanes past the pass's sources count and store nothing
+  const int64_t my_src = on ? a.src[lane] : -1;
+  unsigned long long gap = 0, cross = 0, orphan = 0;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBlock / kWave);
+  for (int64_t r = static_cast<int64_t>(blockIdx.x) * (kMsBlock / kWave) + wave; r < g.rows; r += stride) {
+    const int64_t u = g.lo + r;
+    const eid_t rs = g.row_off[r], re = g.row_off[r + 1];
+    DBFS_DCHECK(rs >= 0 && rs <= re && re <= g.nnz, 24, r);
+    DBFS_DCHECK(u < a.lvl_rows, 25, u);
+    const int lu = lvl[u * kMsSources + lane];
+    const bool ru = on && lu != kNone;
+    const bool is_src = u == my_src;
+    bool has_par = false;
+    uint32_t par = kMsNoParent;
+    // parents only: a row is walked while some lane still looks for its parent
+    bool walk = rs < re;
+    if (!kCount) walk = walk && __ballot(ru && !is_src) != 0ull;
+    for (eid_t e = rs; walk && e < re; e += kWave) {
+      const int cnt = static_cast<int>(min(static_cast<eid_t>(kWave), re - e));
+      const vid_t mine = lane < cnt ? g.col[e + lane] : 0u;
+      DBFS_DCHECK(static_cast<int64_t>(mine) < a.lvl_rows, 26, mine);
+      for (int j = 0; j < cnt; j += kMsCheckAhead) {
+        vid_t w[kMsCheckAhead];
+        int lw[kMsCheckAhead];
+#pragma unroll
+        for (int i = 0; i < kMsCheckAhead; ++i) {
+          w[i] = static_cast<vid_t>(__builtin_amdgcn_readlane(static_cast<int>(mine), min(j + i, cnt - 1)));
+          lw[i] = lvl[static_cast<int64_t>(w[i]) * kMsSources + lane];
+        }
+#pragma unroll
+        for (int i = 0; i < kMsCheckAhead; ++i) {
+          const bool valid = j + i < cnt;  // (wave-uniform)
+          const bool rw = lw[i] != kNone;
+          if (kCount) {
+            const int d = lu - lw[i];
+            if (valid && on && ru != rw) ++cross;
+            if (valid && ru && rw && (d > 1 || d < -1)) ++gap;
+          }
+          if (valid && ru && rw && lw[i] + 1 == lu && !has_par) {
+            has_par = true;
+            par = w[i];
+          }
+        }
+        if (!kCount && __ballot(ru && !is_src && !has_par) == 0ull) {
+          walk = false;
+          break;
+        }
+      }
+    }
+    if (kCount && (is_src ? lu != 0 : (ru && !has_par))) ++orphan;
+    if (kParent && on) a.par[r * kMsSources + lane] = is_src ? static_cast<uint32_t>(u) : par;
+  }
+  if (kCount) {
+    if (gap) atomicAdd(&s_cnt[kMsCheckCounters * lane + 0], gap);
+    if (cross) atomicAdd(&s_cnt[kMsCheckCounters * lane + 1], cross);
+    if (orphan) atomicAdd(&s_cnt[kMsCheckCounters * lane + 2], orphan);
+    __syncthreads();
+    if (t < kMsSources * kMsCheckCounters && s_cnt[t])
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.out) + t, s_cnt[t]);
+  }
+}
+
+template <class L>
+void ms_check_launch(const MsCheckArgs& a, hipStream_t st) {
+  const unsigned grid = grid_for(a.g.rows, kMsBlock / kWave, kMsCheckGrid);
+  if (a.out && a.par) ms_check_kernel<L, true, true><<<grid, kMsBlock, 0, st>>>(a);
+  else if (a.out) ms_check_kernel<L, true, false><<<grid, kMsBlock, 0, st>>>(a);
+  else ms_check_kernel<L, false, true><<<grid, kMsBlock, 0, st>>>(a);
+}
+
+void ms_check(const MsCheckArgs& a, hipStream_t st) {
+  if (a.g.rows <= 0 || (!a.out && !a.par)) return;
+  if (a.lvl_bytes == 2) ms_check_launch<uint16_t>(a, st);
+  else ms_check_launch<uint8_t>(a, st);
 }
 
 void ms_init(const MsInitArgs& a, hipStream_t st) {

@@ -655,6 +655,15 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def_readonly("depth", &BatchResult::depth)
       .def_readonly("dist_sum", &BatchResult::dist_sum)
       .def_readonly("discovered", &BatchResult::discovered)
+      .def_readonly("check_ms", &BatchResult::check_ms)
+      // run_batch(validate=True): per source (gap, cross, orphan); else empty
+      .def_property_readonly("violations",
+                             [](const BatchResult& r) {
+                               py::list out;
+                               for (size_t i = 0; i + 2 < r.violations.size(); i += kMsCheckCounters)
+                                 out.append(py::make_tuple(r.violations[i], r.violations[i + 1], r.violations[i + 2]));
+                               return out;
+                             })
       // per level of each pass: (pass, level, form 'P' push / 'L' pull, active vertices, their edges, ms)
       .def_property_readonly("levels",
                              [](const BatchResult& r) {
@@ -712,16 +721,49 @@ PYBIND11_MODULE(_dbfs_native, m) {
           py::arg("sources"))
       .def(
           "run_batch",
-          [](Engine& e, const std::vector<int64_t>& sources, const std::string& direction, bool levels) {
+          [](Engine& e, const std::vector<int64_t>& sources, const std::string& direction, bool levels, bool validate,
+             bool parents) {
             const BatchDirection d = parse_batch_direction(direction);
             BatchResult r;
             {
               py::gil_scoped_release rel;
-              r = e.run_batch(sources, d, levels);
+              r = e.run_batch(sources, d, levels, validate, parents);
             }
             return r;
           },
-          py::arg("sources"), py::arg("direction") = "auto", py::arg("levels") = true)
+          py::arg("sources"), py::arg("direction") = "auto", py::arg("levels") = true, py::arg("validate") = false,
+          py::arg("parents") = false)
+      .def("gather_batch_parents",
+           [](Engine& e) {
+             std::vector<int64_t> v;
+             int64_t k = 0;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_batch_parents();
+               k = e.batch_parent_sources();
+             }
+             py::array_t<int64_t> a = to_numpy(v);
+             a.resize({static_cast<py::ssize_t>(k), static_cast<py::ssize_t>(k ? v.size() / k : 0)});
+             return a;
+           })
+      // the count form of the batch check on the last pass's resident level
+      // matrix, against `sources`: int64 [k, 3] (gap, cross, orphan)
+      .def(
+          "validate_batch_pass",
+          [](Engine& e, const std::vector<int64_t>& sources) {
+            std::vector<int64_t> v;
+            {
+              py::gil_scoped_release rel;
+              v = e.validate_batch_pass(sources);
+            }
+            py::array_t<int64_t> a = to_numpy(v);
+            a.resize({static_cast<py::ssize_t>(sources.size()), static_cast<py::ssize_t>(kMsCheckCounters)});
+            return a;
+          },
+          py::arg("sources"))
+      // test hook: one entry of the resident level matrix (level < 0: unreached)
+      .def("debug_set_batch_level", &Engine::debug_set_batch_level, py::arg("slot"), py::arg("vertex"),
+           py::arg("level"), py::call_guard<py::gil_scoped_release>())
       .def("gather_batch_levels",
            [](Engine& e) {
              std::vector<lvl_t> v;

@@ -67,12 +67,24 @@ class BatchResult:
     level L).  ``levels``: per level of each pass a tuple (pass, level, form,
     active vertices, their edges, host ms), form 'P' push or 'L' pull.  ``wide_levels``:
     the levels are 16-bit (a pass deeper than 254 levels, in this batch or an
-    earlier one, was rerun)."""
+    earlier one, was rerun).
+
+    With ``run_batch(validate=True)``: ``violations``, per source a tuple
+    (gap, cross, orphan) of the device check's counts over the directed
+    adjacency entries -- both ends reached and more than one level apart, one
+    end reached and the other not, a reached vertex other than the source
+    without a neighbour one level closer (or the source not at level 0) -- and
+    ``validated``, True when every count is zero; both None when the check was
+    not asked for.  ``check_ms``: wall time of the per-pass checks (validation
+    and parents), which ``ms`` never includes; 0.0 without them."""
 
     __slots__ = ("sources", "ms", "gteps", "passes", "wide_levels", "reached", "edges", "depth", "dist_sum",
-                 "discovered", "levels")
+                 "discovered", "levels", "violations", "validated", "check_ms")
 
-    def __init__(self, r: Any):
+    def __init__(self, r: Any, validate: bool = False):
+        self.violations = [tuple(int(x) for x in v) for v in r.violations] if validate else None
+        self.validated = all(v == (0, 0, 0) for v in self.violations) if validate else None
+        self.check_ms = float(r.check_ms)
         self.sources, self.ms, self.gteps, self.passes = list(r.sources), r.ms, r.gteps, r.passes
         self.wide_levels = bool(r.wide_levels)
         self.reached, self.edges, self.depth = list(r.reached), list(r.edges), list(r.depth)
@@ -167,22 +179,41 @@ class BFS:
         the engine's own).  Collective like run()."""
         return [BFSResult.from_native(r) for r in self.engine.run_many([int(s) for s in sources])]
 
-    def run_batch(self, sources, direction: str = "auto", levels: bool = True) -> BatchResult:
+    def run_batch(self, sources, direction: str = "auto", levels: bool = True, validate: bool = False,
+                  parents: bool = False) -> BatchResult:
         """One concurrent traversal from all ``sources`` (64 per pass, one bit
         per source in a 64-bit word per vertex); collective like run().
         ``direction``: "auto" picks push or pull per level (one rank; several
         ranks always pull), "push" / "pull" / "alternate" force a form.
         ``levels=False`` keeps no level matrix (64 bytes per vertex on the
         device): the totals are the same, batch_levels() then raises.  The
-        single-source state of run() is left alone."""
+        single-source state of run() is left alone.
+
+        ``validate=True`` checks every pass's level matrix on the device
+        against every edge, for all its sources at once (Graph500's level
+        rules, as validate() for one source): ``BatchResult.violations`` /
+        ``validated``.  ``parents=True`` also keeps every source's parent tree
+        for batch_parents().  Both read the level matrix (``levels=True``) and
+        run after each pass's timed window: ``BatchResult.check_ms``, never
+        ``ms``."""
         if direction not in BATCH_DIRECTIONS:
             raise ValueError(f"direction must be one of {BATCH_DIRECTIONS}")
-        return BatchResult(self.engine.run_batch([int(s) for s in sources], direction, bool(levels)))
+        if (validate or parents) and not levels:
+            raise ValueError("validate and parents read the level matrix: levels=True")
+        return BatchResult(self.engine.run_batch([int(s) for s in sources], direction, bool(levels), bool(validate),
+                                                 bool(parents)), validate=bool(validate))
 
     def batch_levels(self) -> np.ndarray:
         """Levels of the last run_batch as int32 [k, n] (UNREACHED where a
         source does not reach); collective."""
         return self.engine.gather_batch_levels()
+
+    def batch_parents(self) -> np.ndarray:
+        """Parent trees of the last run_batch(parents=True) as int64 [k, n]:
+        row i is source i's tree with the convention of parents() (a neighbour
+        one level closer, the first in the stored row; parent[source] = source;
+        -1 unreached); collective.  k x n x 8 bytes on the host."""
+        return self.engine.gather_batch_parents()
 
     def levels(self) -> np.ndarray:
         """Full per-vertex level array of the last run (collective)."""

@@ -48,6 +48,32 @@ def levels_are_consistent(csr, levels, src: int) -> bool:
     return bool(np.all(has_parent[reached]))
 
 
+def batch_levels_violations(csr, levels_row, src: int) -> Tuple[int, int, int]:
+    """(gap, cross, orphan) of one source's levels (a row of
+    ``BFS.batch_levels()``), counted exactly as the device check of
+    ``run_batch(validate=True)`` counts them -- its host reference.  Over the
+    directed adjacency entries (u, w) as stored, self-loops and duplicates
+    included: gap = both ends reached and more than one level apart; cross =
+    exactly one end reached; orphan = reached vertices other than ``src``
+    without a neighbour one level closer, plus one if ``src`` is not at level
+    0 (unreached included)."""
+    lv = np.asarray(levels_row, dtype=np.int64)
+    ro = np.asarray(csr.row_off)
+    col = np.asarray(csr.col).astype(np.int64)
+    n = lv.size
+    rows = np.repeat(np.arange(n), np.diff(ro))
+    lu, lw = lv[rows], lv[col]
+    ru, rw = lu != UNREACHED, lw != UNREACHED
+    both = ru & rw
+    cross = int(np.count_nonzero(ru != rw))
+    gap = int(np.count_nonzero(both & (np.abs(lu - lw) > 1)))
+    has_parent = np.zeros(n, dtype=bool)
+    has_parent[rows[both & (lw == lu - 1)]] = True
+    lone = (lv != UNREACHED) & ~has_parent
+    lone[src] = lv[src] != 0
+    return gap, cross, int(np.count_nonzero(lone))
+
+
 def parents_are_valid(csr, levels, parents, src: int) -> bool:
     """Graph500 parent-tree check: every reached v != src has an edge to
     parent[v] and level[parent[v]] == level[v] - 1; unreached have -1."""

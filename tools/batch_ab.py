@@ -7,7 +7,11 @@ traversals, on one GPU:
 Per graph: 64 roots from sample_roots(64, seed=5202611); after a warm-up of
 both, run_many(roots) (sum of ms; the baseline) and run_batch(roots,
 levels=False) alternate `reps` times; medians, spread and the ratio are
-printed, and per-source reached / edges / depth are asserted equal.  Then one
+printed, and per-source reached / edges / depth of every timed batch are
+asserted equal to run_many's.  That the batch's levels are right is the device
+check's statement: one more run_batch(roots, validate=True) keeps the level
+matrix and every source must come back clean (its time, check_ms, is printed
+too).  Then one
 forced-push and one forced-pull batch, level by level: a level's active set is
 the same in both, so the table shows where each form is cheaper -- what the
 direction constants (csrc/engine/batch.cpp) are chosen from."""
@@ -60,9 +64,12 @@ for name, params in graphs:
         for i, r in enumerate(many):
             assert (r.reached, r.edges, r.depth) == (batch.reached[i], batch.edges[i], batch.depth[i]), \
                 (name, roots[i], (r.reached, r.edges, r.depth), (batch.reached[i], batch.edges[i], batch.depth[i]))
+    checked = bfs.run_batch(roots, validate=True)
+    assert checked.validated, (name, [(roots[i], v) for i, v in enumerate(checked.violations) if v != (0, 0, 0)])
     mm, mb = statistics.median(t_many), statistics.median(t_batch)
     forms = "".join(l[2] for l in batch.levels)
-    print(f"\n## {name}: n {bfs.n}, directed edges {E}, {len(roots)} roots, totals equal", flush=True)
+    print(f"\n## {name}: n {bfs.n}, directed edges {E}, {len(roots)} roots, totals equal, every source validated on the device "
+          f"(check {checked.check_ms:.3f} ms)", flush=True)
     print(f"run_many  sum  {spread(t_many)}")
     print(f"run_batch auto {spread(t_batch)}  forms {forms if len(forms) <= 40 else forms[:40] + '...'} "
           f"(P {forms.count('P')}, L {forms.count('L')})")
