@@ -16,10 +16,20 @@
 namespace dbfs {
 namespace {
 
-// Level of a new vertex in the wide or the narrow array (HIP: store_level).
-inline void put_level(lvl_t* wide, uint8_t* narrow, int64_t i, lvl_t level, uint8_t base) {
-  if (narrow) narrow[i] = static_cast<uint8_t>(base + (level <= kNarrowMaxLevel ? level : kNarrowMaxLevel + 1));
-  else wide[i] = level;
+// A level's decision from its totals and its stamp (HIP: finish_level); c:
+// the control block the decision starts from.
+inline void finish_level(const LevelStamp& s, LevelCtrl c, int64_t cnt, int64_t deg) {
+  level_ctrl_finish(c, cnt, deg, s.seed, s.seed ? nullptr : s.rec);
+  *s.ctrl = c;
+  if (LevelMailbox* mb = s.mailbox) {
+    mb->done = c.done;
+    mb->vis_deg = c.vis_deg;
+    mb->next_dir = c.dir;
+    mb->n_f = c.n_f;
+    mb->m_f = c.m_f;
+    mb->reached = c.reached;
+    mb->level = s.seed ? -1 : s.level;
+  }
 }
 
 inline bool test_bit(const word_t* bm, uint64_t v) { return (bm[v >> 6] >> (v & 63)) & 1ull; }
@@ -84,10 +94,8 @@ class CpuBackend final : public Backend {
       return;
     }
     bool use_bytes = a.cand_bytes != nullptr;
-    if (a.ctrl) {
-      if (!chain_live(*a.ctrl, 'T', a.max_mf)) return;
-      use_bytes = use_bytes && a.ctrl->bytes != 0;
-    }
+    if (!a.guard.live()) return;
+    if (a.guard.ctrl) use_bytes = use_bytes && a.guard.ctrl->bytes != 0;
     const int64_t nunits = div_up(a.words, kUnitWords);
     for (int64_t u = 0; u < nunits; ++u) {
       int64_t cnt = 0, deg = 0;
@@ -95,7 +103,7 @@ class CpuBackend final : public Backend {
         word_t c = 0;
         if (use_bytes && a.level_direct) {
           for (int b = 0; b < 64; ++b)
-            if (a.level_direct[w * 64 + b] == static_cast<uint8_t>(a.narrow_base + a.new_level)) c |= 1ull << b;
+            if (a.level_direct[w * 64 + b] == a.out.byte()) c |= 1ull << b;
         } else if (use_bytes) {
           c = gather_bytes(a.cand_bytes + w * 64);
         } else {
@@ -111,7 +119,7 @@ class CpuBackend final : public Backend {
           const int b = __builtin_ctzll(x);
           x &= x - 1;
           const int64_t v = w * 64 + b;
-          put_level(a.level, a.level8, v, a.new_level, a.narrow_base);
+          a.out.store(v);
           const eid_t d = a.g.row_off[v + 1] - a.g.row_off[v];
           if (d > 0) { ++cnt; deg += d; }
         }
@@ -124,12 +132,12 @@ class CpuBackend final : public Backend {
   void level_ctrl_init(LevelCtrl* c, const LevelCtrl& init) override { *c = init; }
   void init_run(const InitRunArgs& a) override {
     const int64_t src = a.src_local;
-    if (a.level8 && a.level8_filled) {
-      if (src >= 0) a.level8[src] = a.narrow_base;
+    if (a.out.level8 && a.level8_filled) {
+      if (src >= 0) a.out.level8[src] = a.out.narrow_base;
     } else {
       for (int64_t i = 0; i < a.g.rows; ++i) {
-        if (a.level8) a.level8[i] = i == src ? a.narrow_base : kNarrowUnreached;
-        else a.level[i] = i == src ? 0 : kUnreached;
+        if (a.out.level8) a.out.level8[i] = i == src ? a.out.narrow_base : kNarrowUnreached;
+        else a.out.level[i] = i == src ? 0 : kUnreached;
       }
     }
     for (int64_t w = 0; w < a.gwords; ++w) a.visited[w] = a.zdeg[w];
@@ -161,14 +169,14 @@ class CpuBackend final : public Backend {
     }
     a.stats[0] = a.stats[2] = cnt;
     a.stats[1] = a.stats[3] = deg;
-    a.qscan[cnt] = deg;
+    a.wl.qscan[cnt] = deg;
     if (a.frontier_clear)
       for (int64_t w = 0; w < a.words; ++w) a.frontier_clear[w] = 0;
-    if (cnt && a.qbase) {
-      a.qscan[0] = 0;
-      a.qbase[0] = a.g.row_off[src];
-      a.qv[0] = static_cast<vid_t>(src);
-      for (int64_t b = 0; b * kTdEdgesPerBlock < deg; ++b) a.blk_vstart[b] = 0;
+    if (cnt && a.wl.qbase) {
+      a.wl.qscan[0] = 0;
+      a.wl.qbase[0] = a.g.row_off[src];
+      a.wl.qv[0] = static_cast<vid_t>(src);
+      for (int64_t b = 0; b * kTdEdgesPerBlock < deg; ++b) a.wl.blk_vstart[b] = 0;
     }
     if (a.ctrl) {
       int64_t gc = cnt, gd = deg;
@@ -178,18 +186,7 @@ class CpuBackend final : public Backend {
         a.stats[2] = gc;
         a.stats[3] = gd;
       }
-      LevelCtrl c = a.ctrl_init;
-      level_ctrl_finish(c, gc, gd, true, nullptr);
-      *a.ctrl = c;
-      if (a.mailbox) {
-        a.mailbox->done = c.done;
-        a.mailbox->vis_deg = c.vis_deg;
-        a.mailbox->next_dir = c.dir;
-        a.mailbox->n_f = c.n_f;
-        a.mailbox->m_f = c.m_f;
-        a.mailbox->reached = c.reached;
-        a.mailbox->level = -1;
-      }
+      finish_level({a.ctrl, nullptr, a.mailbox, -1, true}, a.ctrl_init, gc, gd);
     }
   }
   void publish_stats(const int64_t* stats, StatsMailbox* mb, int64_t seq) override {
@@ -347,7 +344,7 @@ class CpuBackend final : public Backend {
   void free_mapped(void* h) override { std::free(h); }
 
   void scan_units(const ScanArgs& a) override {
-    if (a.ctrl && !chain_live(*a.ctrl, a.expect_dir, a.expect_cap)) return;
+    if (!a.guard.live()) return;
     const int64_t nchunks = div_up(a.nunits, kScanChunk);
     int64_t c = 0, d = 0;
     for (int64_t k = 0; k < nchunks; ++k) {
@@ -367,18 +364,7 @@ class CpuBackend final : public Backend {
     a.stats[0] = a.stats[2] = c;
     a.stats[1] = a.stats[3] = d;
     a.qscan[c] = d;
-    if (a.ctrl && a.finish) {
-      level_ctrl_finish(*a.ctrl, c, d, a.seed, a.seed ? nullptr : a.rec);
-      if (a.mailbox) {
-        a.mailbox->done = a.ctrl->done;
-        a.mailbox->vis_deg = a.ctrl->vis_deg;
-        a.mailbox->next_dir = a.ctrl->dir;
-        a.mailbox->n_f = a.ctrl->n_f;
-        a.mailbox->m_f = a.ctrl->m_f;
-        a.mailbox->reached = a.ctrl->reached;
-        a.mailbox->level = a.level;
-      }
-    }
+    if (a.stamp.ctrl && a.finish) finish_level(a.stamp, *a.stamp.ctrl, c, d);
   }
 
   void zero_degree_mask(const ZeroDegArgs& a) override {
@@ -393,7 +379,7 @@ class CpuBackend final : public Backend {
   }
 
   void compact_frontier(const CompactArgs& a) override {
-    if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
+    if (!a.guard.live()) return;
     const int64_t nunits = div_up(a.words, kUnitWords);
     for (int64_t u = 0; u < nunits; ++u) {
       int64_t pos = a.unit_cnt_off[u] + a.part_cnt[u / kScanChunk];
@@ -408,11 +394,11 @@ class CpuBackend final : public Backend {
           const int64_t v = w * 64 + b;
           const eid_t rs = a.g.row_off[v], d = a.g.row_off[v + 1] - rs;
           if (d <= 0) continue;
-          a.qscan[pos] = off;
-          a.qbase[pos] = rs - off;
-          if (a.qv) a.qv[pos] = static_cast<vid_t>(v);
+          a.wl.qscan[pos] = off;
+          a.wl.qbase[pos] = rs - off;
+          if (a.wl.qv) a.wl.qv[pos] = static_cast<vid_t>(v);
           for (int64_t blk = div_up(off, kTdEdgesPerBlock); blk * kTdEdgesPerBlock < off + d; ++blk)
-            a.blk_vstart[blk] = static_cast<int32_t>(pos);
+            a.wl.blk_vstart[blk] = static_cast<int32_t>(pos);
           ++pos;
           off += d;
         }
@@ -423,22 +409,21 @@ class CpuBackend final : public Backend {
   void td_expand(const TdArgs& a) override {
     int64_t q = a.q;
     bool bytes = a.next_bytes != nullptr;
-    if (a.ctrl) {
-      if (!chain_live(*a.ctrl, 'T', a.max_mf)) return;
+    if (!a.guard.live()) return;
+    if (a.guard.ctrl) {
       q = a.dev_stats[0];
-      bytes = a.ctrl->bytes != 0;
-      if (a.clear_qv)
-        for (int64_t i = 0; i < q; ++i)
-          a.clear_frontier[a.clear_qv[i] >> 6] = 0;
+      bytes = a.guard.ctrl->bytes != 0;
+      if (a.clear_frontier)
+        for (int64_t i = 0; i < q; ++i) a.clear_frontier[a.in.qv[i] >> 6] = 0;
     }
     // a split level's part (TdArgs::split_k): its run of the level's edges
-    const int64_t m = a.ctrl ? a.dev_stats[1] : a.m;
+    const int64_t m = a.guard.ctrl ? a.dev_stats[1] : a.m;
     const int64_t e_lo = a.split_k > 1 ? m * a.split_i / a.split_k : 0;
     const int64_t e_hi = a.split_k > 1 ? m * (a.split_i + 1) / a.split_k : m;
     for (int64_t i = 0; i < q; ++i) {
-      const int64_t b = std::max(a.qscan[i], e_lo), e = std::min(a.qscan[i + 1], e_hi);
+      const int64_t b = std::max(a.in.qscan[i], e_lo), e = std::min(a.in.qscan[i + 1], e_hi);
       for (int64_t k = b; k < e; ++k) {
-        const vid_t v = a.g.col[k + a.qbase[i]];
+        const vid_t v = a.g.col[k + a.in.qbase[i]];
         // (the filter's clear bits are visited vertices: skipping on them
         // changes nothing -- and catches a filter that drops an unvisited one)
         if (a.unvis && !test_bit(a.unvis, unvis_index(v, a.unvis_mult))) continue;
@@ -447,7 +432,7 @@ class CpuBackend final : public Backend {
           vid_t* list = a.lists + static_cast<int64_t>(v / a.part) * (a.list_cap + 1);
           list[1 + list[0]++] = v;
         } else if (bytes && a.level_direct) {
-          a.level_direct[v] = static_cast<uint8_t>(a.narrow_base + a.new_level);
+          a.level_direct[v] = a.out.byte();
         } else if (bytes) {
           a.next_bytes[v] = 1;
         } else {
@@ -458,14 +443,14 @@ class CpuBackend final : public Backend {
   }
 
   void td_binned(const BinArgs& a) override {
-    if (!chain_live(*a.ctrl, 'T', 0)) return;
+    if (!a.guard.live()) return;
     const int64_t q = a.dev_stats[0];
-    if (a.clear_qv)
-      for (int64_t i = 0; i < q; ++i) a.clear_frontier[a.clear_qv[i] >> 6] = 0;
+    if (a.clear_frontier)
+      for (int64_t i = 0; i < q; ++i) a.clear_frontier[a.in.qv[i] >> 6] = 0;
     std::vector<word_t> nb(static_cast<size_t>(a.words), 0);
     for (int64_t i = 0; i < q; ++i)
-      for (int64_t k = a.qscan[i]; k < a.qscan[i + 1]; ++k) {
-        const vid_t v = a.g.col[k + a.qbase[i]];
+      for (int64_t k = a.in.qscan[i]; k < a.in.qscan[i + 1]; ++k) {
+        const vid_t v = a.g.col[k + a.in.qbase[i]];
         if (!test_bit(a.visited, v)) nb[v >> 6] |= 1ull << (v & 63);
       }
     for (int64_t w = 0; w < a.words; ++w) {
@@ -475,19 +460,8 @@ class CpuBackend final : public Backend {
   }
 
   void level_finish(const LevelFinishArgs& a) override {
-    if (!a.seed && !chain_live(*a.ctrl, a.expect_dir, a.expect_cap)) return;
-    LevelCtrl c = a.seed ? a.ctrl_init : *a.ctrl;
-    level_ctrl_finish(c, a.stats[2], a.stats[3], a.seed, a.seed ? nullptr : a.rec);
-    *a.ctrl = c;
-    if (a.mailbox) {
-      a.mailbox->done = c.done;
-      a.mailbox->vis_deg = c.vis_deg;
-      a.mailbox->next_dir = c.dir;
-      a.mailbox->n_f = c.n_f;
-      a.mailbox->m_f = c.m_f;
-      a.mailbox->reached = c.reached;
-      a.mailbox->level = a.seed ? -1 : a.level;
-    }
+    if (!a.stamp.seed && !a.guard.live()) return;
+    finish_level(a.stamp, a.stamp.seed ? a.ctrl_init : *a.stamp.ctrl, a.stats[2], a.stats[3]);
   }
 
   // Sparse top-down level (see the HIP kernel): claims in the replicated
@@ -497,27 +471,27 @@ class CpuBackend final : public Backend {
   void sparse_settle(const TdSparseArgs& a, vid_t v) {
     const int64_t r = static_cast<int64_t>(v) - a.g.lo;
     DBFS_CHECK(r >= 0 && r < a.g.rows, "sparse level: settled vertex outside this shard");
-    put_level(a.level, a.level8, r, a.new_level, a.narrow_base);
+    a.out.store(r);
     const eid_t rs = a.g.row_off[r], d = a.g.row_off[r + 1] - rs;
     if (d <= 0) return;
     a.frontier_out[r >> 6] |= 1ull << (r & 63);
     const int64_t cnt = sparse_cnt_, deg = sparse_deg_;
-    a.oscan[cnt] = deg;
-    a.obase[cnt] = rs - deg;
-    a.oqv[cnt] = static_cast<vid_t>(r);
+    a.next.qscan[cnt] = deg;
+    a.next.qbase[cnt] = rs - deg;
+    a.next.qv[cnt] = static_cast<vid_t>(r);
     for (int64_t blk = div_up(deg, kTdEdgesPerBlock); blk * kTdEdgesPerBlock < deg + d; ++blk)
-      a.oblk[blk] = static_cast<int32_t>(cnt);
+      a.next.blk_vstart[blk] = static_cast<int32_t>(cnt);
     ++sparse_cnt_;
     sparse_deg_ += d;
   }
   void sparse_finish_totals(const TdSparseArgs& a) {
     a.stats[0] = a.stats[2] = sparse_cnt_;
     a.stats[1] = a.stats[3] = sparse_deg_;
-    a.oscan[sparse_cnt_] = sparse_deg_;
+    a.next.qscan[sparse_cnt_] = sparse_deg_;
   }
   void td_sparse(const TdSparseArgs& a) override {
     DBFS_CHECK(!a.direct.active, "CpuBackend: no direct list exchange (peer windows are GPU memory)");
-    if (!chain_live(*a.ctrl, 'T', a.max_mf)) return;
+    if (!a.guard.live()) return;
     // the input frontier's rows [col_begin, col_end), in work-list order (a
     // bitmap input: its set bits in (word, bit) order, as a compaction lists them)
     std::vector<std::pair<eid_t, eid_t>> rows;
@@ -531,8 +505,9 @@ class CpuBackend final : public Backend {
       }
     } else {
       const int64_t q = a.dev_stats[0];
-      for (int64_t i = 0; i < q; ++i) a.frontier_in[a.qv[i] >> 6] = 0;
-      for (int64_t i = 0; i < q; ++i) rows.emplace_back(a.qscan[i] + a.qbase[i], a.qscan[i + 1] + a.qbase[i]);
+      for (int64_t i = 0; i < q; ++i) a.frontier_in[a.in.qv[i] >> 6] = 0;
+      for (int64_t i = 0; i < q; ++i)
+        rows.emplace_back(a.in.qscan[i] + a.in.qbase[i], a.in.qscan[i + 1] + a.in.qbase[i]);
     }
     sparse_cnt_ = sparse_deg_ = 0;
     for (const auto& [cb, ce] : rows) {
@@ -552,20 +527,11 @@ class CpuBackend final : public Backend {
     }
     if (a.lists) return;  // several ranks: td_sparse_apply finishes
     sparse_finish_totals(a);
-    level_ctrl_finish(*a.ctrl, sparse_cnt_, sparse_deg_, false, a.rec);
-    if (a.mailbox) {
-      a.mailbox->done = a.ctrl->done;
-      a.mailbox->vis_deg = a.ctrl->vis_deg;
-      a.mailbox->next_dir = a.ctrl->dir;
-      a.mailbox->n_f = a.ctrl->n_f;
-      a.mailbox->m_f = a.ctrl->m_f;
-      a.mailbox->reached = a.ctrl->reached;
-      a.mailbox->level = a.level_index;
-    }
+    finish_level(a.stamp, *a.stamp.ctrl, sparse_cnt_, sparse_deg_);
   }
   void td_sparse_apply(const TdSparseArgs& a) override {
     DBFS_CHECK(!a.direct.active, "CpuBackend: no direct list exchange (peer windows are GPU memory)");
-    if (!chain_live(*a.ctrl, 'T', a.max_mf)) return;
+    if (!a.guard.live()) return;
     for (int r = 0; r < a.nranks; ++r) {
       const vid_t* list = a.recv_lists + static_cast<int64_t>(r) * a.list_stride;
       for (vid_t k = 0; k < list[0]; ++k) {
@@ -587,9 +553,6 @@ class CpuBackend final : public Backend {
   uint64_t check_ = 0;
 
   void list_scatter(const ListScatterArgs& a) override {
-    if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
-    if (a.reset_lists)
-      for (int r = 0; r < a.nranks; ++r) a.reset_lists[static_cast<int64_t>(r) * (a.list_cap + 1)] = 0;
     for (int r = 0; r < a.nranks; ++r) {
       const vid_t* list = a.lists + static_cast<int64_t>(r) * (a.list_cap + 1);
       for (vid_t k = 0; k < list[0]; ++k) {
@@ -600,8 +563,7 @@ class CpuBackend final : public Backend {
   }
 
   void pack_bytes(const PackArgs& a) override {
-    if (a.ctrl && (a.ctrl->done || (a.flag ? a.ctrl->dir != 'B' || !*a.flag : a.ctrl->dir != 'T' || !a.ctrl->bytes)))
-      return;
+    if (!a.guard.live() || (a.guard.ctrl && !(a.flag ? *a.flag : a.guard.ctrl->bytes))) return;
     for (int64_t w = 0; w < a.words; ++w)
       if (w < a.skip_begin || w >= a.skip_end) a.next[w] |= gather_bytes(a.bytes + w * 64);
   }
@@ -620,7 +582,7 @@ class CpuBackend final : public Backend {
       std::copy(d.begin(), d.end(), a.scan.unit_deg);
       return;
     }
-    if (a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) return;
+    if (!a.guard.live()) return;
     // hub-cut level (as the HIP kernel): claimed vertices join the output
     // unscanned, the others find parents among the frontier hubs only
     const bool cut = a.cut_edges > 0 && *a.cut_flag;
@@ -635,13 +597,13 @@ class CpuBackend final : public Backend {
             const int64_t v = w * 64 + b;
             const bool claimed =
                 a.cut_claim ? a.cut_claim[v] != 0
-                            : a.level8[v] == static_cast<uint8_t>(a.narrow_base +
-                                                                  std::min<lvl_t>(a.new_level, kNarrowMaxLevel + 1));
+                            : a.out.level8[v] == static_cast<uint8_t>(a.out.narrow_base +
+                                                                      std::min<lvl_t>(a.out.new_level, kNarrowMaxLevel + 1));
             if (!((a.visited[w] >> b) & 1ull) && claimed) {
               pw |= 1ull << b;
               if (a.cut_claim) {
                 a.cut_claim[v] = 0;
-                a.level[v] = a.new_level;
+                a.out.level[v] = a.out.new_level;
               }
             }
           }
@@ -658,7 +620,7 @@ class CpuBackend final : public Backend {
           for (eid_t e = a.g.row_off[v]; e < a.g.row_off[v + 1]; ++e) {
             if (test_bit(a.frontier, a.g.col[e]) && (!cut || test_bit(a.g.hub_bits, a.g.col[e]))) {
               out |= 1ull << b;
-              put_level(a.level, a.level8, v, a.new_level, a.narrow_base);
+              a.out.store(v);
               ++cnt;
               deg += a.g.row_off[v + 1] - a.g.row_off[v];
               break;
@@ -866,7 +828,7 @@ class CpuBackend final : public Backend {
     return k;
   }
   void hub_gather(const HubGatherArgs& a) override {
-    if (a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) return;
+    if (!a.guard.live()) return;
     for (int64_t w = 0; w < div_up(a.g.nhubs, 64); ++w) {
       word_t m = 0;
       int64_t d = 0;
@@ -883,13 +845,13 @@ class CpuBackend final : public Backend {
     if (a.cut_part) {
       int64_t hub_edges = 0;
       for (int64_t w = 0; w < div_up(a.g.nhubs, 64); ++w) hub_edges += a.cut_part[w];
-      *a.cut_flag = a.ctrl->m_f - hub_edges <= a.cut_edges ? 1 : 0;
+      *a.cut_flag = a.guard.ctrl->m_f - hub_edges <= a.cut_edges ? 1 : 0;
     }
     if (a.visited)
       for (int64_t i = 0; i < a.words; ++i) a.visited[i] |= a.frontier[i];
   }
   void bu_cut_prep(const BuArgs& a) override {
-    if (a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) return;
+    if (!a.guard.live()) return;
     if (!*a.cut_flag) return;
     const bool x = a.cut_bytes != nullptr;
     DBFS_CHECK(x || a.g.lo == 0, "bu_cut_prep: a shard past vertex 0 needs the several-rank arguments");
@@ -908,14 +870,14 @@ class CpuBackend final : public Backend {
             continue;
           }
           if (a.cut_claim) a.cut_claim[r] = 1;
-          else put_level(nullptr, a.level8, r, a.new_level, a.narrow_base);
+          else a.out.store(r);
         }
       }
   }
   void bu_cut_merge(const BuArgs& a) override {
-    DBFS_CHECK(a.cut_flag && a.cut_recv && a.cut_next && (a.level8 || a.cut_claim) && a.cut_nranks > 1,
+    DBFS_CHECK(a.cut_flag && a.cut_recv && a.cut_next && (a.out.level8 || a.cut_claim) && a.cut_nranks > 1,
                "bu_cut_merge: several ranks' hub-cut arguments missing");
-    if (a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) return;
+    if (!a.guard.live()) return;
     if (!*a.cut_flag) return;
     for (int64_t w = 0; w < a.words; ++w) {
       word_t c = 0;
@@ -927,31 +889,31 @@ class CpuBackend final : public Backend {
       for (c &= ~a.visited[w]; c; c &= c - 1) {
         const int64_t r = w * 64 + __builtin_ctzll(c);
         if (a.cut_claim) a.cut_claim[r] = 1;
-        else put_level(nullptr, a.level8, r, a.new_level, a.narrow_base);
+        else a.out.store(r);
       }
     }
   }
   void hub_apply(const HubApplyArgs& a) override {
-    if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
+    if (!a.guard.live()) return;
     for (int64_t h = 0; h < a.g.td_nhubs; ++h) {
       if (!a.mark[h]) continue;
       const vid_t v = a.g.td_hub_vertex[h];
-      a.level8[v] = static_cast<uint8_t>(a.narrow_base + a.new_level);
+      a.out.level8[v] = a.out.byte();
       a.mark[h] = 0;
     }
   }
   void refresh_visited(const RefreshArgs& a) override {
-    if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
-    const uint8_t lv = static_cast<uint8_t>(a.narrow_base + a.new_level);
+    if (!a.guard.live()) return;
+    const uint8_t lv = a.out.byte();
     for (int64_t w = 0; w < a.words; ++w) {
       word_t m = 0;
       for (int b = 0; b < 64; ++b)
-        if (a.level8[w * 64 + b] == lv) m |= 1ull << b;
+        if (a.out.level8[w * 64 + b] == lv) m |= 1ull << b;
       a.visited[w] |= m;
     }
   }
   void hub_visited(const HubVisitedArgs& a) override {
-    if (a.ctrl && !chain_live(*a.ctrl, 'T', 0)) return;
+    if (!a.guard.live()) return;
     for (int64_t w = 0; w < div_up(a.g.td_nhubs, 64); ++w) {
       word_t m = 0;
       for (int b = 0; b < 64 && w * 64 + b < a.g.td_nhubs; ++b)
@@ -960,7 +922,7 @@ class CpuBackend final : public Backend {
     }
   }
   void unvis_filter(const UnvisArgs& a) override {
-    if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
+    if (!a.guard.live()) return;
     std::fill(a.out, a.out + kUnvisWords, word_t(0));
     for (int64_t v = 0; v < a.n; ++v)
       if (!test_bit(a.visited, static_cast<vid_t>(v))) {

@@ -40,6 +40,9 @@ class DeviceLoop {
     char d = 'T';       // form: 'T', 'S', 'X', 'B'
     char pf = 'I';      // the previous level's form ('I': the seed)
     int64_t cap = 0;    // sparse: the global frontier edges it stays live for
+    // what every kernel of the chain tests at entry: {ctrl, the level's
+    // enqueued direction, cap}, built once in enqueue_level
+    ChainGuard guard;
     double mf_hint = -1;
     int cur = 0;        // input frontier buffer (level L reads frontier_[(L + 1) & 1])
     bool in_gathered = false;  // the input frontier is global already
@@ -119,16 +122,20 @@ class DeviceLoop {
     return e_.stats_.data() + static_cast<int64_t>((L + 1) % blocks) * e_.stats_stride_;
   }
   static int slot(int level) { return (level + 1) % kMailboxSlots; }
-  // work-list set k (level L reads set L & 1; one set without sparse levels)
-  int64_t* qscan_set(int k) const { return sparse_ && (k & 1) ? e_.qscan2_.data() : e_.qscan_.data(); }
-  int64_t* qbase_set(int k) const { return sparse_ && (k & 1) ? e_.qbase2_.data() : e_.qbase_.data(); }
-  int32_t* blk_set(int k) const { return sparse_ && (k & 1) ? e_.blk_vstart2_.data() : e_.blk_vstart_.data(); }
+  // work list of level L: set L & 1 with its vertex map; without sparse
+  // levels one set and no map
+  WorkList work_list(int L) const {
+    if (!sparse_) return {e_.qscan_.data(), e_.qbase_.data(), e_.blk_vstart_.data(), nullptr};
+    if (L & 1) return {e_.qscan2_.data(), e_.qbase2_.data(), e_.blk_vstart2_.data(), e_.qv_[1].data()};
+    return {e_.qscan_.data(), e_.qbase_.data(), e_.blk_vstart_.data(), e_.qv_[0].data()};
+  }
   uint32_t* group_tickets();
   bool cells_fit() const { return e_.g_.rows() < (int64_t(1) << 32) && e_.g_.nnz() < (int64_t(1) << 40); }
   const volatile LevelMailbox* wait_stamp(int lv);
-  LevelFinishArgs finish_args(int level, bool seed, char expect_dir, int64_t cap);
-  void finish_ranks(int level, bool seed, char expect_dir, int64_t cap, bool gather);
-  ScanArgs scan_args(int level, bool seed, char expect_dir, int64_t cap);
+  LevelStamp stamp(int level, bool seed = false);
+  LevelFinishArgs finish_args(int level, const ChainGuard& guard);
+  void finish_ranks(int level, const ChainGuard& guard, bool gather);
+  ScanArgs scan_args(int level, const ChainGuard& guard);
 
   // ---- planner ----
   char td_form(int L, double mf, int64_t* cap, bool exact) const;
@@ -200,7 +207,7 @@ void DeviceLoop::setup() {
     e_.mailbox_dev_ = static_cast<LevelMailbox*>(dptr);
   }
   // one rank with narrow levels: byte-map levels write the levels directly
-  direct_ = !xc_ && e_.run_narrow_ && opt_.td_direct;
+  direct_ = !xc_ && e_.level_out(0).level8 && opt_.td_direct;
   byte_edges_ = direct_ ? opt_.td_direct_edges : opt_.td_byte_edges;
   bytes_ok_ = opt_.mode != Mode::BottomUp && byte_edges_ <= e_.total_directed_;
   if (bytes_ok_ && !e_.next_bytes_.data()) {
@@ -317,17 +324,17 @@ const volatile LevelMailbox* DeviceLoop::wait_stamp(int lv) {
   return mb;
 }
 
-LevelFinishArgs DeviceLoop::finish_args(int level, bool seed, char expect_dir, int64_t cap) {
+// Where level `level` is stamped when it finishes.
+LevelStamp DeviceLoop::stamp(int level, bool seed) {
+  return {e_.ctrl_.data(), seed ? nullptr : e_.rec_at(level), e_.mailbox_dev_ + slot(level), level, seed};
+}
+
+LevelFinishArgs DeviceLoop::finish_args(int level, const ChainGuard& guard) {
   LevelFinishArgs fa;
   fa.stats = sblk(level);
-  fa.ctrl = e_.ctrl_.data();
   fa.ctrl_init = init_;
-  fa.rec = seed ? nullptr : e_.rec_at(level);
-  fa.mailbox = e_.mailbox_dev_ + slot(level);
-  fa.level = level;
-  fa.seed = seed;
-  fa.expect_dir = expect_dir;
-  fa.expect_cap = cap;
+  fa.guard = guard;
+  fa.stamp = stamp(level);
   return fa;
 }
 
@@ -337,16 +344,16 @@ LevelFinishArgs DeviceLoop::finish_args(int level, bool seed, char expect_dir, i
 // in the same launch the level's output frontier slice all-gathered
 // (Comm::allgather_allreduce) -- then level_finish decides and stamps.
 // (bfs_mpi.cu:615-621 pays a Sendrecv and an Allreduce per level.)
-void DeviceLoop::finish_ranks(int level, bool seed, char expect_dir, int64_t cap, bool gather) {
+void DeviceLoop::finish_ranks(int level, const ChainGuard& guard, bool gather) {
   int64_t* blk = sblk(level);
-  // level L writes frontier_[L & 1] (the seed: frontier_[1])
-  const int out = seed ? 1 : (level & 1);
-  const LevelFinishArgs fa = finish_args(level, seed, expect_dir, cap);
+  // level L writes frontier_[L & 1]
+  const int out = level & 1;
+  const LevelFinishArgs fa = finish_args(level, guard);
   comm_.level_end(fr_own(out), e_.frontier_[out].data(), gather ? static_cast<size_t>(W_) * sizeof(word_t) : 0,
                   blk + 2, 2, fa);
 }
 
-ScanArgs DeviceLoop::scan_args(int level, bool seed, char expect_dir, int64_t cap) {
+ScanArgs DeviceLoop::scan_args(int level, const ChainGuard& guard) {
   ScanArgs sa;
   sa.unit_cnt = e_.unit_cnt_.data();
   sa.unit_deg = e_.unit_deg_.data();
@@ -355,14 +362,9 @@ ScanArgs DeviceLoop::scan_args(int level, bool seed, char expect_dir, int64_t ca
   sa.part_deg = e_.part_deg_.data();
   sa.ticket = e_.ticket_.data();
   sa.stats = sblk(level);
-  sa.qscan = qscan_set(level + 1);
-  sa.ctrl = e_.ctrl_.data();
-  sa.rec = seed ? nullptr : e_.rec_at(level);
-  sa.mailbox = e_.mailbox_dev_ + slot(level);
-  sa.level = level;
-  sa.seed = seed;
-  sa.expect_dir = expect_dir;
-  sa.expect_cap = cap;
+  sa.qscan = work_list(level + 1).qscan;
+  sa.guard = guard;
+  sa.stamp = stamp(level);
   sa.finish = !xc_;
   return sa;
 }
@@ -515,6 +517,7 @@ void DeviceLoop::enqueue_level(int L, char d, int64_t cap, double mf_hint, bool 
   res_.chains.push_back({L, d, enq_cap_[L], enq_gather_[L] != 0});
   res_.chains.back().push = c.push != nullptr;
   c.cap = enq_cap_[L];
+  c.guard = {e_.ctrl_.data(), enq_dir_[L], c.cap};
   c.mf_hint = mf_hint;
   c.cur = (L + 1) & 1;
   char trace_name[48];
@@ -539,10 +542,9 @@ void DeviceLoop::enqueue_level(int L, char d, int64_t cap, double mf_hint, bool 
     case 'T': emit_dense(c); break;
     default: emit_bottom_up(c); break;
   }
-  if (!c.fused_scan) be_.scan_units(scan_args(L, false, enq_dir_[L], c.cap));
+  if (!c.fused_scan) be_.scan_units(scan_args(L, c.guard));
   enq_fused_[L] = c.fused_scan && d != 'S' && !c.folded;
-  if (xc_ && !c.level_ended)
-    finish_ranks(L, false, enq_dir_[L], c.cap, enq_gather_[L] && !c.push);
+  if (xc_ && !c.level_ended) finish_ranks(L, c.guard, enq_gather_[L] && !c.push);
   if (opt_.phase_timing) evs_[L] = {ev0, be_.record_event()};
   if (ht_) hmark("enqueued " + std::to_string(L));
 }
@@ -554,8 +556,8 @@ void DeviceLoop::compact(const Chain& c, word_t* clear_all) {
   const int L = c.L;
   if (L > 0 && enq_fused_[static_cast<size_t>(L - 1)]) {
     // the previous level only finished its totals: its unit prefixes now (no
-    // finish; a no-op unless this chain is live)
-    ScanArgs sa = scan_args(L - 1, false, 'T', c.d == 'S' ? c.cap : 0);
+    // finish; under this chain's guard: a no-op unless this chain is live)
+    ScanArgs sa = scan_args(L - 1, c.guard);
     sa.finish = false;
     be_.scan_units(sa);
   }
@@ -567,16 +569,10 @@ void DeviceLoop::compact(const Chain& c, word_t* clear_all) {
   ca.unit_deg_off = e_.unit_deg_.data();
   ca.part_cnt = e_.part_cnt_.data();
   ca.part_deg = e_.part_deg_.data();
-  ca.qscan = qscan_set(L);
-  ca.qbase = qbase_set(L);
-  ca.blk_vstart = blk_set(L);
-  if (sparse_) {
-    ca.qv = e_.qv_[L & 1].data();
-    ca.clear = fr_own(c.cur);
-  }
+  ca.wl = work_list(L);
+  if (sparse_) ca.clear = fr_own(c.cur);
   ca.clear_all = clear_all;
-  ca.ctrl = e_.ctrl_.data();
-  ca.max_mf = c.d == 'S' ? c.cap : 0;
+  ca.guard = c.guard;
   be_.compact_frontier(ca);
 }
 
@@ -599,33 +595,21 @@ void DeviceLoop::emit_sparse(Chain& c) {
   else if (compacted) compact(c, c.pf == 'B' ? fr_own(c.cur ^ 1) : nullptr);
   TdSparseArgs sp;
   sp.g = gv_;
-  sp.qscan = qscan_set(L);
-  sp.qbase = qbase_set(L);
-  sp.blk_vstart = blk_set(L);
-  sp.qv = e_.qv_[L & 1].data();
+  sp.in = work_list(L);
   sp.dev_stats = sblk(L - 1);
   sp.frontier_in = fr_own(c.cur);
   sp.frontier_out = fr_own(c.cur ^ 1);
   sp.visited = e_.visited_.data();
-  sp.level = e_.level_.data();
-  sp.level8 = e_.run_narrow_ ? e_.level8_.data() : nullptr;
-  sp.narrow_base = e_.narrow_base_;
-  sp.new_level = L + 1;
-  sp.oscan = qscan_set(L + 1);
-  sp.obase = qbase_set(L + 1);
-  sp.oblk = blk_set(L + 1);
-  sp.oqv = e_.qv_[(L + 1) & 1].data();
+  sp.out = e_.level_out(L + 1);
+  sp.next = work_list(L + 1);
   sp.counter = e_.sparse_cnt_.data() + ((L + 1) & 1);
   sp.ticket = e_.sparse_ticket_.data();
   sp.stats = sblk(L);
-  sp.ctrl = e_.ctrl_.data();
-  sp.rec = e_.rec_at(L);
-  sp.mailbox = e_.mailbox_dev_ + slot(L);
-  sp.level_index = L;
+  sp.guard = c.guard;
+  sp.stamp = stamp(L);
   sp.grid = std::max<int64_t>(1, opt_.td_sparse_grid);
   sp.late_ticks = late_ticks_;
   sp.first = !compacted || from_bits;
-  sp.max_mf = c.cap;
   if (from_bits) {
     sp.from_bits = true;
     sp.words = W_;
@@ -643,7 +627,7 @@ void DeviceLoop::emit_sparse(Chain& c) {
   sp.lists = e_.dl_send_lists_.data();
   sp.list_stride = e_.list_stride_;
   sp.part = part_.part;
-  sp.mailbox = nullptr;
+  sp.stamp.mailbox = nullptr;
   // the exchange itself: by the two kernels through the peers' windows
   // (direct), or a collective between them
   const size_t lcap = static_cast<size_t>(c.cap > 0 ? c.cap : list_max_);
@@ -674,7 +658,7 @@ void DeviceLoop::emit_sparse(Chain& c) {
   if (sp.fuse_apply) {
     sp.recv_lists = nullptr;
     if (comm_.direct_level_end(2, &sp.end)) {
-      sp.fin = finish_args(L, false, enq_dir_[L], c.cap);
+      sp.fin = finish_args(L, c.guard);
       c.level_ended = true;
     } else {
       sp.fuse_apply = false;  // (not taken: the level ends in its collective)
@@ -690,7 +674,7 @@ void DeviceLoop::emit_sparse(Chain& c) {
                          lcap);
   sp.recv_lists = direct ? nullptr : e_.dl_recv_lists_.data();
   if (end_ok && comm_.direct_level_end(2, &sp.end)) {
-    sp.fin = finish_args(L, false, enq_dir_[L], c.cap);
+    sp.fin = finish_args(L, c.guard);
     c.level_ended = true;
   }
   sp.grid = apply_grid;
@@ -710,15 +694,10 @@ void DeviceLoop::emit_binned(Chain& c) {
   if (!listed) compact(c, nullptr);
   BinArgs xa;
   xa.g = gv_;
-  xa.qscan = qscan_set(L);
-  xa.qbase = qbase_set(L);
-  xa.blk_vstart = blk_set(L);
+  xa.in = work_list(L);
   xa.dev_stats = sblk(L - 1);
-  if (listed) {
-    xa.clear_qv = e_.qv_[L & 1].data();
-    xa.clear_frontier = fr_own(c.cur);
-  }
-  xa.ctrl = e_.ctrl_.data();
+  if (listed) xa.clear_frontier = fr_own(c.cur);
+  xa.guard = c.guard;
   xa.shift = bin_shift_;
   xa.nbins = static_cast<int>(nbins_);
   xa.grid = kBinGrid;
@@ -737,22 +716,27 @@ void DeviceLoop::emit_binned(Chain& c) {
   tu.clear_cand = false;
   tu.force = true;
   tu.frontier = fr_own(c.cur ^ 1);
-  tu.new_level = L + 1;
-  tu.ctrl = e_.ctrl_.data();
+  tu.out.new_level = L + 1;
+  tu.guard = c.guard;
   be_.update_frontier(tu);
 }
 
 // The update's fused finish: the level's totals (and with one rank its
-// decision) in its last workgroup, as bottom-up.
+// decision) in its last workgroup, as bottom-up -- per-workgroup totals slots
+// and a two-level ticket, no scan launch unless a compaction follows.
+// RMAT-26 1344 / 1341 -> 1363 / 1353 GTEPS; top-down only equal within noise.
+// (A first version with one workgroup per 4 units and totals atomics on one
+// address: level 1 of RMAT-26 38 -> 117 us.)
 void DeviceLoop::fuse_update(Chain& c, UpdateArgs& tu) {
   if (!e_.td_tot_.data()) e_.td_tot_ = DBuf<int64_t>(be_, static_cast<size_t>(2 * kMaxFusedGrid + 2 * kFusedGroups));
   tu.fuse_scan = true;
-  tu.scan = scan_args(c.L, false, enq_dir_[c.L], c.cap);
-  // small graphs: the next compaction's unit prefixes too (no scan_units launch)
-  tu.fold_scan = opt_.fold_scan && e_.nunits_ <= kFoldScanUnits;
+  tu.scan = scan_args(c.L, c.guard);
+  // graphs of at most kFoldScanUnits units: the next compaction's unit
+  // prefixes too (one scan_units launch less per dense level)
+  tu.fold_scan = e_.nunits_ <= kFoldScanUnits;
   c.folded = tu.fold_scan;
   tu.tot = e_.td_tot_.data();
-  if (opt_.td_group_ticket) tu.group_ticket = group_tickets();
+  tu.group_ticket = group_tickets();
   c.fused_scan = true;
 }
 
@@ -766,15 +750,10 @@ void DeviceLoop::emit_dense(Chain& c) {
   if (!listed) compact(c, nullptr);
   TdArgs ta;
   ta.g = gv_;
-  ta.qscan = qscan_set(L);
-  ta.qbase = qbase_set(L);
-  ta.blk_vstart = blk_set(L);
-  if (listed) {
-    ta.clear_qv = e_.qv_[L & 1].data();
-    ta.clear_frontier = fr_own(c.cur);
-  }
+  ta.in = work_list(L);
+  if (listed) ta.clear_frontier = fr_own(c.cur);
   ta.visited = e_.visited_.data();
-  ta.ctrl = e_.ctrl_.data();
+  ta.guard = c.guard;
   ta.dev_stats = sblk(L - 1);
   ta.grid = td_grid_;
   ta.grid_filter = td_grid_filter_;
@@ -806,8 +785,7 @@ void DeviceLoop::emit_dense(Chain& c) {
     uv.mult = unvis_mult(gv_.n);
     uv.out = e_.unvis_.data();
     uv.pop = e_.unvis_pop_.data();
-    uv.ctrl = e_.ctrl_.data();
-    uv.max_mf = 0;
+    uv.guard = c.guard;
     be_.unvis_filter(uv);
     ta.unvis = e_.unvis_.data();
     ta.unvis_mult = uv.mult;
@@ -825,7 +803,7 @@ void DeviceLoop::emit_dense(Chain& c) {
     hv.g = gv_;
     hv.visited = e_.visited_.data();
     hv.out = e_.td_hub_vis_.data();
-    hv.ctrl = e_.ctrl_.data();
+    hv.guard = c.guard;
     hv.min_edges = opt_.td_hub_edges;
     hv.vis_frac = opt_.td_hub_vis_frac;
     be_.hub_visited(hv);
@@ -835,13 +813,11 @@ void DeviceLoop::emit_dense(Chain& c) {
   }
   // (a level past kNarrowMaxLevel would store the unreached byte: the usual
   // path flags the overflow and the run is repeated wide)
-  if (direct_ && e_.run_narrow_ && L + 1 <= kNarrowMaxLevel) {
+  ta.out = e_.level_out(L + 1);
+  if (direct_ && L + 1 <= kNarrowMaxLevel) {
     // byte-map levels write the level itself (nothing to clear after)
-    ta.level_direct = e_.level8_.data();
-    ta.narrow_base = e_.narrow_base_;
-    ta.new_level = L + 1;
-    tu.level_direct = e_.level8_.data();
-    tu.narrow_base = e_.narrow_base_;
+    ta.level_direct = ta.out.level8;
+    tu.level_direct = ta.out.level8;
     // Hub marks become level bytes (hub_apply), which only the direct form's
     // update reads back; the device picks the form by the level's edges.  So
     // marks only when every level the hub filter can run on (>= td_hub_edges
@@ -872,19 +848,15 @@ void DeviceLoop::emit_dense(Chain& c) {
   if (parts > 1) {
     res_.chains.back().split = parts;
     RefreshArgs ra;
-    ra.level8 = ta.level_direct;
-    ra.narrow_base = ta.narrow_base;
-    ra.new_level = ta.new_level;
+    ra.out = ta.out;
     ra.visited = e_.visited_.data();
     ra.words = GW_;
-    ra.ctrl = e_.ctrl_.data();
-    ra.max_mf = ta.max_mf;
+    ra.guard = c.guard;
     ta.split_k = parts;
     for (int i = 0; i < parts; ++i) {
       ta.split_i = i;
       be_.td_expand(ta);
       // (the input list's frontier words cleared, the level stamped: once)
-      ta.clear_qv = nullptr;
       ta.clear_frontier = nullptr;
       if (i + 1 < parts) be_.refresh_visited(ra);
     }
@@ -895,11 +867,8 @@ void DeviceLoop::emit_dense(Chain& c) {
     HubApplyArgs ha;
     ha.g = gv_;
     ha.mark = ta.td_hub_mark;
-    ha.level8 = ta.level_direct;
-    ha.narrow_base = ta.narrow_base;
-    ha.new_level = ta.new_level;
-    ha.ctrl = e_.ctrl_.data();
-    ha.max_mf = ta.max_mf;
+    ha.out = ta.out;
+    ha.guard = c.guard;
     be_.hub_apply(ha);
   }
   tu.cand = e_.next_.data();
@@ -912,7 +881,7 @@ void DeviceLoop::emit_dense(Chain& c) {
       pa.bytes = e_.next_bytes_.data();
       pa.next = e_.next_.data();
       pa.words = GW_;
-      pa.ctrl = e_.ctrl_.data();
+      pa.guard = c.guard;
       be_.pack_bytes(pa);
     }
     comm_.alltoall(e_.next_.data(), e_.recv_.data(), static_cast<size_t>(W_) * sizeof(word_t));
@@ -927,22 +896,19 @@ void DeviceLoop::emit_dense(Chain& c) {
   // level byte of this level is a new vertex, as every `next` bit is)
   tu.force = parts > 1;
   tu.frontier = fr_own(c.cur ^ 1);
-  tu.new_level = L + 1;
-  tu.ctrl = e_.ctrl_.data();
+  tu.out.new_level = L + 1;
+  tu.guard = c.guard;
   tu.push = c.push;
   tu.push_rank = me_;
   tu.push_nranks = P_;
-  if (opt_.td_fused_finish) {
-    // totals (and with one rank the decision) in the update's last
-    // workgroup (as bottom-up)
-    fuse_update(c, tu);
-    // several ranks: the level's end in the same last workgroup (no frontier
-    // gathered, or a pushed one)
-    if (xc_ && cells_fit() && (!enq_gather_[L] || c.push) &&
-        comm_.direct_level_end(2, &tu.end)) {
-      tu.fin = finish_args(L, false, enq_dir_[L], c.cap);
-      c.level_ended = true;
-    }
+  // totals (and with one rank the decision) in the update's last workgroup
+  // (as bottom-up)
+  fuse_update(c, tu);
+  // several ranks: the level's end in the same last workgroup (no frontier
+  // gathered, or a pushed one)
+  if (xc_ && cells_fit() && (!enq_gather_[L] || c.push) && comm_.direct_level_end(2, &tu.end)) {
+    tu.fin = finish_args(L, c.guard);
+    c.level_ended = true;
   }
   be_.update_frontier(tu);
 }
@@ -959,10 +925,7 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
   ba.visited = e_.visited_.data() + me_ * W_;
   ba.frontier = e_.frontier_[c.cur].data();
   ba.new_frontier = fr_own(c.cur ^ 1);
-  ba.level = e_.level_.data();
-  ba.level8 = e_.run_narrow_ ? e_.level8_.data() : nullptr;
-  ba.narrow_base = e_.narrow_base_;
-  ba.new_level = L + 1;
+  ba.out = e_.level_out(L + 1);
   ba.words = W_;
   ba.lane_limit = opt_.bu_lane_limit;
   ba.whole_units = opt_.bu_whole_units;
@@ -978,7 +941,7 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
   ba.follow_up = c.pf == 'B';
   ba.unit_cnt = e_.unit_cnt_.data();
   ba.unit_deg = e_.unit_deg_.data();
-  ba.ctrl = e_.ctrl_.data();
+  ba.guard = c.guard;
   ba.push = c.push;
   ba.push_rank = me_;
   ba.push_nranks = P_;
@@ -988,7 +951,7 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
     hg.g = gv_;
     hg.frontier = e_.frontier_[c.cur].data();
     hg.hub_front = e_.hub_front_.data();
-    hg.ctrl = e_.ctrl_.data();
+    hg.guard = c.guard;
     if (c.pull) {
       // the peers' slices pushed by the previous level's kernels
       hg.pull = c.pull;
@@ -1035,7 +998,7 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
     if (cut) {
       ba.cut_edges = opt_.bu_cut_edges;
       ba.cut_flag = e_.cut_flag_.data();
-      if (!e_.run_narrow_) {
+      if (!ba.out.level8) {
         // wide levels: claims in a byte array of their own (kept zero)
         if (!e_.cut_claim_.data()) {
           e_.cut_claim_ = DBuf<uint8_t>(be_, static_cast<size_t>(W_ * kWordBits));
@@ -1064,7 +1027,7 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
         pa.bytes = e_.next_bytes_.data();
         pa.next = e_.next_.data();
         pa.words = GW_;
-        pa.ctrl = e_.ctrl_.data();
+        pa.guard = c.guard;
         pa.flag = e_.cut_flag_.data();
         pa.skip_begin = me_ * W_;
         pa.skip_end = (me_ + 1) * W_;
@@ -1078,24 +1041,21 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
       }
     }
   }
-  if (opt_.bu_fused_scan) {
-    // the level's totals (and with one rank its finish) in the bottom-up
-    // kernel's last workgroup; the unit prefixes only if a top-down chain
-    // follows
-    if (!e_.bu_tot_.data()) e_.bu_tot_ = DBuf<int64_t>(be_, static_cast<size_t>(2 * kMaxFusedGrid));
-    ba.fuse_scan = true;
-    ba.scan = scan_args(L, false, enq_dir_[L], c.cap);
-    ba.tot = e_.bu_tot_.data();
-    c.fused_scan = true;
-    // several ranks: the level's end in the kernel's last workgroup too (no
-    // frontier gather; the hub kernels' fused finish) -- on a hub-cut level
-    // in whichever of its two kernels the decision runs (the plain one on a
-    // no-op chain)
-    if (xc_ && cells_fit() && gv_.nhubs > 0 && (!enq_gather_[L] || c.push) &&
-        comm_.direct_level_end(2, &ba.end)) {
-      ba.fin = finish_args(L, false, enq_dir_[L], c.cap);
-      c.level_ended = true;
-    }
+  // the level's totals (and with one rank its finish: direction decision,
+  // mailbox stamp) in the bottom-up kernel's last-arriving workgroup instead
+  // of a scan launch; the unit prefixes only if a top-down chain follows
+  if (!e_.bu_tot_.data()) e_.bu_tot_ = DBuf<int64_t>(be_, static_cast<size_t>(2 * kMaxFusedGrid));
+  ba.fuse_scan = true;
+  ba.scan = scan_args(L, c.guard);
+  ba.tot = e_.bu_tot_.data();
+  c.fused_scan = true;
+  // several ranks: the level's end in the kernel's last workgroup too (no
+  // frontier gather; the hub kernels' fused finish) -- on a hub-cut level
+  // in whichever of its two kernels the decision runs (the plain one on a
+  // no-op chain)
+  if (xc_ && cells_fit() && gv_.nhubs > 0 && (!enq_gather_[L] || c.push) && comm_.direct_level_end(2, &ba.end)) {
+    ba.fin = finish_args(L, c.guard);
+    c.level_ended = true;
   }
   be_.bu_step(ba);
 }
@@ -1151,9 +1111,7 @@ RunResult DeviceLoop::run() {
     if (seed_gather_) ia.frontier_global = e_.frontier_[1].data();
   }
   if (sparse_) {
-    ia.qbase = e_.qbase_.data();
-    ia.blk_vstart = e_.blk_vstart_.data();
-    ia.qv = e_.qv_[0].data();
+    ia.wl = work_list(0);
     ia.frontier_clear = fr_own(0);
   }
   // (the previous traversal left both owned slices zero: 16 B per vertex of
@@ -1173,9 +1131,7 @@ RunResult DeviceLoop::run() {
   ua_.cand_stride = W_;
   ua_.clear_cand = !xc_;
   ua_.visited = e_.visited_.data() + me_ * W_;
-  ua_.level = e_.level_.data();
-  ua_.level8 = e_.run_narrow_ ? e_.level8_.data() : nullptr;
-  ua_.narrow_base = e_.narrow_base_;
+  ua_.out = e_.level_out(0);  // (new_level: per chain)
   ua_.words = W_;
   ua_.unit_cnt = e_.unit_cnt_.data();
   ua_.unit_deg = e_.unit_deg_.data();

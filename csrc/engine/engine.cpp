@@ -796,10 +796,8 @@ InitRunArgs Engine::init_args(int64_t source, word_t* seed_frontier, LevelCtrl* 
   const int me = comm_.rank();
   InitRunArgs ia;
   ia.g = g_.view();
-  ia.level = level_.data();
-  ia.level8 = run_narrow_ ? level8_.data() : nullptr;
+  ia.out = level_out(0);
   ia.level8_filled = level8_filled_;
-  ia.narrow_base = narrow_base_;
   ia.zdeg = zdeg_.data();
   ia.visited = visited_.data();
   ia.gwords = part_.global_words();
@@ -812,7 +810,7 @@ InitRunArgs Engine::init_args(int64_t source, word_t* seed_frontier, LevelCtrl* 
   ia.part_cnt = part_cnt_.data();
   ia.part_deg = part_deg_.data();
   ia.stats = stats_.data();
-  ia.qscan = qscan_.data();
+  ia.wl.qscan = qscan_.data();
   ia.ctrl = ctrl;
   ia.ctrl_init = ctrl_init;
   ia.mailbox = mailbox;
@@ -901,10 +899,7 @@ RunResult Engine::run_bitmap(int64_t source) {
     ua.force = force;
     ua.visited = vis_own;
     ua.frontier = fr_nxt_own();
-    ua.level = level_.data();
-    ua.level8 = run_narrow_ ? level8_.data() : nullptr;
-    ua.narrow_base = narrow_base_;
-    ua.new_level = new_level;
+    ua.out = level_out(new_level);
     ua.words = W;
     ua.unit_cnt = unit_cnt_.data();
     ua.unit_deg = unit_deg_.data();
@@ -989,15 +984,11 @@ RunResult Engine::run_bitmap(int64_t source) {
           ca.unit_deg_off = unit_deg_.data();
           ca.part_cnt = part_cnt_.data();
           ca.part_deg = part_deg_.data();
-          ca.qscan = qscan_.data();
-          ca.qbase = qbase_.data();
-          ca.blk_vstart = blk_vstart_.data();
+          ca.wl = {qscan_.data(), qbase_.data(), blk_vstart_.data(), nullptr};
           be_.compact_frontier(ca);
           TdArgs ta;
           ta.g = gv;
-          ta.qscan = qscan_.data();
-          ta.qbase = qbase_.data();
-          ta.blk_vstart = blk_vstart_.data();
+          ta.in = ca.wl;
           ta.q = q_local;
           ta.m = m_local;
           ta.visited = visited_.data();
@@ -1062,10 +1053,7 @@ RunResult Engine::run_bitmap(int64_t source) {
       ba.visited = vis_own;
       ba.frontier = fr_cur();
       ba.new_frontier = fr_nxt_own();
-      ba.level = level_.data();
-      ba.level8 = run_narrow_ ? level8_.data() : nullptr;
-      ba.narrow_base = narrow_base_;
-      ba.new_level = L + 1;
+      ba.out = level_out(L + 1);
       ba.words = W;
       ba.lane_limit = opt_.bu_lane_limit;
       ba.whole_units = opt_.bu_whole_units;

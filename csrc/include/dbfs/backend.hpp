@@ -233,6 +233,74 @@ DBFS_HD void level_ctrl_finish(LevelCtrl& c, int64_t count, int64_t degsum, bool
   c.check_visited = static_cast<double>(c.vis_deg) >= c.check_visited_min * c.total_directed ? 1 : 0;
 }
 
+// A device-loop chain's kernels run only when the chain is live: the level is
+// not done, its direction is the one the chain was enqueued for, and (sparse
+// top-down chains) the global frontier edges are at most the chain's cap.
+DBFS_HD bool chain_live(const LevelCtrl& c, int32_t dir, int64_t cap) {
+  return !c.done && (dir == 0 || c.dir == dir) && (cap <= 0 || c.m_f <= cap);
+}
+
+// What every kernel of a chain tests at entry, built once per chain
+// (DeviceLoop::enqueue_level).  No control block: the host loop, always live.
+// (Kernels that carry a collective run its part on a no-op chain too.)
+struct ChainGuard {
+  const LevelCtrl* ctrl = nullptr;
+  int32_t dir = 0;   // 'T' / 'B' (0: any)
+  int64_t cap = 0;   // live while ctrl->m_f <= cap (0: no bound)
+  DBFS_HD bool live() const { return !ctrl || chain_live(*ctrl, dir, cap); }
+};
+
+// Where a finished level is stamped (device loop): the control block the
+// decision updates, the level's record (not for the seed) and its mailbox slot.
+struct LevelStamp {
+  LevelCtrl* ctrl = nullptr;
+  LevelRecDev* rec = nullptr;
+  LevelMailbox* mailbox = nullptr;  // device-mapped pinned slot
+  int32_t level = 0;
+  bool seed = false;
+};
+
+// Where new vertices' levels go (Engine::level_out): the narrow array (one
+// byte per vertex, narrow_base + level; kNarrowUnreached = not reached) when
+// the run uses one, else the 32-bit array.
+struct LevelOut {
+  lvl_t* level = nullptr;       // rows
+  uint8_t* level8 = nullptr;    // rows, instead of `level` when set
+  uint8_t narrow_base = 0;      // narrow level bytes of this run: base + level (kNarrowEpochs)
+  lvl_t new_level = 0;
+  // the byte of new_level (levels up to kNarrowMaxLevel)
+  DBFS_HD uint8_t byte() const { return static_cast<uint8_t>(narrow_base + new_level); }
+  // vertex i reached at new_level (uniform branch).  A level too deep for the
+  // bytes stores base + kNarrowMaxLevel + 1: the engine reruns such a
+  // traversal with wide levels.
+  DBFS_HD void store(int64_t i) const {
+    if (level8)
+      level8[i] = static_cast<uint8_t>(narrow_base + (new_level <= kNarrowMaxLevel ? new_level : kNarrowMaxLevel + 1));
+    else
+      level[i] = new_level;
+  }
+};
+
+// Load-balanced top-down work list of a frontier: qscan[i] = exclusive prefix
+// of degrees (qscan[entries] = their sum), qbase[i] = row_off[v_i] - qscan[i],
+// blk_vstart[b] = index of the entry covering edge b * kTdEdgesPerBlock,
+// qv[i] = v_i (local row; optional).  WorkList for the kernels that write one,
+// WorkListIn for those that read it.
+struct WorkList {
+  int64_t* qscan = nullptr;
+  int64_t* qbase = nullptr;
+  int32_t* blk_vstart = nullptr;
+  vid_t* qv = nullptr;
+};
+struct WorkListIn {
+  const int64_t* qscan = nullptr;
+  const int64_t* qbase = nullptr;
+  const int32_t* blk_vstart = nullptr;
+  const vid_t* qv = nullptr;
+  WorkListIn() = default;
+  WorkListIn(const WorkList& w) : qscan(w.qscan), qbase(w.qbase), blk_vstart(w.blk_vstart), qv(w.qv) {}
+};
+
 // Per-run initialisation of the bitmap engine in one pass (replaces a level
 // fill, a visited copy, the seed update and its scan: ~8 dependent launches):
 //   level[r] = kUnreached (0 for the source), visited = zdeg (+ source bit),
@@ -244,13 +312,8 @@ DBFS_HD void level_ctrl_finish(LevelCtrl& c, int64_t count, int64_t degsum, bool
 //   mailbox slot of level -1 is stamped.
 struct InitRunArgs {
   ShardView g;
-  lvl_t* level = nullptr;          // rows
-  // Narrow level array (one byte per vertex, kNarrowUnreached = not reached;
-  // levels up to kNarrowMaxLevel): written instead of `level` when set, here
-  // and by every bitmap-engine kernel that writes levels.
-  uint8_t* level8 = nullptr;
-  uint8_t narrow_base = 0;             // narrow level bytes of this run: base + level (kNarrowEpochs)
-  bool level8_filled = false;      // level8 already holds kNarrowUnreached (prefilled): only the source's byte
+  LevelOut out;                    // (new_level 0: the source's)
+  bool level8_filled = false;      // out.level8 already holds kNarrowUnreached (prefilled): only the source's byte
   const word_t* zdeg = nullptr;    // global
   word_t* visited = nullptr;       // global
   int64_t gwords = 0;
@@ -263,13 +326,11 @@ struct InitRunArgs {
   int64_t* part_cnt = nullptr;
   int64_t* part_deg = nullptr;
   int64_t* stats = nullptr;
-  int64_t* qscan = nullptr;
-  // Device loop: the seed's work-list entry (source vertex, qbase, the edge
-  // blocks it covers) so a sparse first level can run without a compaction,
-  // and frontier_clear (the first level's output bitmap) zeroed.
-  int64_t* qbase = nullptr;
-  int32_t* blk_vstart = nullptr;
-  vid_t* qv = nullptr;
+  // The seed's work list: its end marker in qscan always; device loop, with
+  // qbase / blk_vstart / qv set: the seed's entry (source vertex, qbase, the
+  // edge blocks it covers) so a sparse first level can run without a
+  // compaction, and frontier_clear (the first level's output bitmap) zeroed.
+  WorkList wl;
   word_t* frontier_clear = nullptr;
   // both owned frontier slices are known zero (the previous traversal ended
   // on a top-down level that found nothing: top-down levels clear their input
@@ -304,22 +365,12 @@ struct ScanArgs {
   unsigned* ticket = nullptr;    // zero before the first launch; reset by the last block
   int64_t* stats = nullptr;
   int64_t* qscan = nullptr;
-  // device-driven loop: skip everything when ctrl->done at entry; the last
-  // workgroup runs level_ctrl_finish and fills rec / the mailbox slot
-  LevelCtrl* ctrl = nullptr;
-  LevelRecDev* rec = nullptr;       // this level's record
-  LevelMailbox* mailbox = nullptr;  // device-mapped pinned slot
-  int32_t level = 0;
-  bool seed = false;
-  // Device loop: the level's chain was enqueued for this direction (0: any);
-  // when ctrl->dir differs, the chain was a no-op and so is the scan.
-  int32_t expect_dir = 0;
-  // ... and, for a multi-rank list-form top-down chain, only valid while the
-  // level's global frontier edges fit its lists (ctrl->m_f <= expect_cap;
-  // 0: no bound).
-  int64_t expect_cap = 0;
-  // Device loop: run level_ctrl_finish here (one rank); several ranks reduce
-  // the totals first and finish in level_finish.
+  // device loop: a no-op on a no-op chain; the last workgroup runs
+  // level_ctrl_finish and stamps the level
+  ChainGuard guard;
+  LevelStamp stamp;
+  // ... here (one rank); several ranks reduce the totals first and finish in
+  // level_finish.
   bool finish = true;
 };
 
@@ -328,22 +379,10 @@ struct ScanArgs {
 // ctrl_init) and stamps rec / the mailbox, as the one-rank scan does.
 struct LevelFinishArgs {
   const int64_t* stats = nullptr;
-  LevelCtrl* ctrl = nullptr;
   LevelCtrl ctrl_init;
-  LevelRecDev* rec = nullptr;
-  LevelMailbox* mailbox = nullptr;
-  int32_t level = 0;
-  bool seed = false;
-  int32_t expect_dir = 0;
-  int64_t expect_cap = 0;  // see ScanArgs::expect_cap
+  ChainGuard guard;  // (not tested for the seed)
+  LevelStamp stamp;
 };
-
-// A device-loop chain's kernels run only when the chain is live: the level is
-// not done, its direction is the one the chain was enqueued for, and (list-form
-// top-down chains) the global frontier edges fit the chain's lists.
-DBFS_HD bool chain_live(const LevelCtrl& c, int32_t dir, int64_t cap) {
-  return !c.done && (dir == 0 || c.dir == dir) && (cap <= 0 || c.m_f <= cap);
-}
 
 // Host-loop statistics mailbox (pinned, device-mapped).  After a level's
 // totals are final (scan, plus the all-reduce on several ranks) one tiny
@@ -356,9 +395,7 @@ struct StatsMailbox {
   int64_t v[4] = {0, 0, 0, 0};
 };
 
-// Owned frontier bitmap -> load-balanced top-down work list:
-// qscan[i] = exclusive prefix of degrees, qbase[i] = row_off[v_i] - qscan[i],
-// blk_vstart[b] = index of the entry covering edge b * kTdEdgesPerBlock.
+// Owned frontier bitmap -> load-balanced top-down work list (WorkList).
 struct CompactArgs {
   ShardView g;
   const word_t* frontier = nullptr;
@@ -367,28 +404,24 @@ struct CompactArgs {
   const int64_t* unit_deg_off = nullptr;
   const int64_t* part_cnt = nullptr;      // chunk prefixes
   const int64_t* part_deg = nullptr;
-  int64_t* qscan = nullptr;
-  int64_t* qbase = nullptr;
-  int32_t* blk_vstart = nullptr;
-  vid_t* qv = nullptr;              // optional: work-list entry -> vertex (local row)
+  WorkList wl;                      // (qv optional)
   word_t* clear = nullptr;          // optional: zero the frontier words once read (== frontier)
   // optional: zero every word of this bitmap (a sparse level after a
   // bottom-up one writes its output into the bottom-up level's input)
   word_t* clear_all = nullptr;
-  const LevelCtrl* ctrl = nullptr;  // device loop: runs only when ctrl->dir == 'T'
-  int64_t max_mf = 0;               // ... and ctrl->m_f <= max_mf (0: any; a sparse chain's compaction)
+  ChainGuard guard;
 };
 
 // Sparse top-down level (device loop, one rank): one kernel instead of
-// compact + td_expand + update + scan.  Expands the work list (qscan / qbase /
-// blk_vstart / qv, totals in dev_stats[0..1]) edge-balanced like td_expand,
+// compact + td_expand + update + scan.  Expands the work list (`in`, totals
+// in dev_stats[0..1]) edge-balanced like td_expand,
 // claims each new vertex with a fetch-or on `visited`, writes its level, sets
 // its bit in frontier_out (clean on entry) and appends it -- wave-aggregated,
 // one packed atomic (count << kSparseEdgeBits | edges) per wave, so entries
-// stay ordered by edge offset -- to the output work list (oscan / obase / oblk
-// / oqv) the next level expands directly.  The input vertices' bits are
+// stay ordered by edge offset -- to the output work list (`next`) the next
+// level expands directly.  The input vertices' bits are
 // cleared from frontier_in (keeps the bitmap the next sparse level writes
-// clean).  The last workgroup publishes the totals (stats[0..3], oscan[q]),
+// clean).  The last workgroup publishes the totals (stats[0..3], next.qscan[q]),
 // runs level_ctrl_finish and stamps rec / the mailbox like the scan.
 constexpr int kSparseEdgeBits = 36;
 // Direct exchanges (peer transport, Comm::direct_lists / direct_level_end):
@@ -459,20 +492,15 @@ struct UpdateArgs {
   bool force = false;
   word_t* visited = nullptr;     // owned slice of the global visited bitmap
   word_t* frontier = nullptr;    // owned slice of the NEXT global frontier bitmap
-  lvl_t* level = nullptr;        // rows
-  uint8_t* level8 = nullptr;     // narrow levels (see InitRunArgs)
-  uint8_t narrow_base = 0;             // narrow level bytes of this run: base + level (kNarrowEpochs)
-  lvl_t new_level = 0;
+  LevelOut out;
   int64_t words = 0;             // words of the owned slice
   int64_t* unit_cnt = nullptr;   // nunits
   int64_t* unit_deg = nullptr;   // nunits
-  // Device loop: runs only when ctrl->dir == 'T'; reads cand_bytes when
-  // ctrl->bytes, else cand (both given).
-  const LevelCtrl* ctrl = nullptr;
-  int64_t max_mf = 0;  // list-form chain: live only while ctrl->m_f <= max_mf
+  // Device loop: reads cand_bytes when guard.ctrl->bytes, else cand (both given).
+  ChainGuard guard;
   // With the byte-map levels of TdArgs::level_direct: candidates are the
-  // unvisited vertices whose level already reads new_level (level8, padded to
-  // whole words); cand_bytes is not read.
+  // unvisited vertices whose level byte already reads out.byte() (level8,
+  // padded to whole words); cand_bytes is not read.
   const uint8_t* level_direct = nullptr;
   // One rank, device loop (as BuArgs::fuse_scan): totals and finish in the
   // last-arriving workgroup, unit statistics left unscanned (a following
@@ -485,12 +513,13 @@ struct UpdateArgs {
   bool fold_scan = false;
   ScanArgs scan;
   int64_t* tot = nullptr;
-  // ... with the ticket two-level: workgroups of kFusedGroup consecutive ids
-  // share a group ticket (kBuQueueStride apart, zero between launches; the
-  // group's last workgroup re-zeroes it, sums the group's slots into
-  // tot[2 kMaxFusedGrid + 2 g] and takes the level ticket), so the grid can
-  // be large without thousands of same-address atomics.  Null: one ticket
-  // (grid capped at kMaxFusedGrid / 8).
+  // ... with the ticket two-level (required with fuse_scan): workgroups of
+  // kFusedGroup consecutive ids share a group ticket (kBuQueueStride apart,
+  // zero between launches; the group's last workgroup re-zeroes it, sums the
+  // group's slots into tot[2 kMaxFusedGrid + 2 g] and takes the level ticket),
+  // so the grid can be large without thousands of same-address atomics.
+  // (Measured against one ticket and a grid of kMaxFusedGrid / 8:
+  // profiles/r2_ab_td_group_ticket.txt.)
   unsigned* group_ticket = nullptr;
   // several ranks: the new frontier words also pushed to the peers (FrontierTable)
   const FrontierTable* push = nullptr;
@@ -509,38 +538,26 @@ struct UpdateArgs {
 
 struct TdSparseArgs {
   ShardView g;
-  const int64_t* qscan = nullptr;
-  const int64_t* qbase = nullptr;
-  const int32_t* blk_vstart = nullptr;
-  const vid_t* qv = nullptr;
+  WorkListIn in;                       // the level's work list
   const int64_t* dev_stats = nullptr;  // [0] entries, [1] edges of the input list
   word_t* frontier_in = nullptr;       // owned slice
   word_t* frontier_out = nullptr;      // owned slice, zero on entry
   word_t* visited = nullptr;           // global
-  lvl_t* level = nullptr;              // rows
-  uint8_t* level8 = nullptr;           // narrow levels (see InitRunArgs)
-  uint8_t narrow_base = 0;             // narrow level bytes of this run: base + level (kNarrowEpochs)
-  int32_t new_level = 0;
-  int64_t* oscan = nullptr;
-  int64_t* obase = nullptr;
-  int32_t* oblk = nullptr;
-  vid_t* oqv = nullptr;
+  LevelOut out;
+  WorkList next;                       // the next level's work list
   unsigned long long* counter = nullptr;  // zero on entry; reset by the last workgroup
   unsigned* ticket = nullptr;             // zero on entry; reset by the last workgroup
   int64_t* stats = nullptr;
-  LevelCtrl* ctrl = nullptr;
-  LevelRecDev* rec = nullptr;
-  LevelMailbox* mailbox = nullptr;
-  int32_t level_index = 0;
+  // (the cap: a sparse chain enqueued for a level that turns out large is a
+  // no-op and is re-enqueued dense)
+  ChainGuard guard;
+  LevelStamp stamp;
   int64_t grid = 0;
   bool first = true;  // first kernel of the level (else a compaction ran before it)
-  // live only while ctrl->m_f <= max_mf (0: any): a sparse chain enqueued for
-  // a level that turns out large is a no-op and is re-enqueued dense
-  int64_t max_mf = 0;
   // from_bits (a level right after a bottom-up one): the input frontier is the
   // bitmap frontier_in itself (`words` owned words, zeroed as read), not a
-  // work list -- no unit scan, no compaction; qscan / qbase / blk_vstart / qv /
-  // dev_stats are unused and frontier_out must be zero on entry.  The kernel's
+  // work list -- no unit scan, no compaction; `in` and dev_stats are unused
+  // and frontier_out must be zero on entry.  The kernel's
   // workgroups end on a two-level ticket (group_ticket: kFusedGroups tickets
   // kBuQueueStride apart, zero between launches).
   bool from_bits = false;
@@ -595,14 +612,12 @@ struct TdSparseArgs {
 // then writes the levels and unit statistics.  Correct for any frontier size.
 struct BinArgs {
   ShardView g;
-  const int64_t* qscan = nullptr;
-  const int64_t* qbase = nullptr;
-  const int32_t* blk_vstart = nullptr;
+  WorkListIn in;
   const int64_t* dev_stats = nullptr;  // [0] work-list entries, [1] frontier edges
-  // work list handed over by a sparse level: zero its vertices' input bits
-  const vid_t* clear_qv = nullptr;
+  // work list handed over by a sparse level (no compaction ran): zero its
+  // vertices' (in.qv) words of clear_frontier
   word_t* clear_frontier = nullptr;
-  const LevelCtrl* ctrl = nullptr;     // runs only when ctrl->dir == 'T'
+  ChainGuard guard;                    // (device loop only: ctrl required)
   int shift = 12;                      // bin = vertex >> shift (bins align with 4096-vertex units)
   int nbins = 0;
   int grid = 0;                        // workgroups of the count / fill passes
@@ -624,9 +639,7 @@ constexpr int kBinMaxBins = 2048;
 // For every edge (u, v) with u in the work list and v not visited: next[v] = 1.
 struct TdArgs {
   ShardView g;
-  const int64_t* qscan = nullptr;
-  const int64_t* qbase = nullptr;
-  const int32_t* blk_vstart = nullptr;
+  WorkListIn in;
   int64_t q = 0;        // work-list entries
   int64_t m = 0;        // work-list edges (qscan[q])
   const word_t* visited = nullptr;  // global
@@ -635,7 +648,7 @@ struct TdArgs {
   // instead of a scattered 64-bit atomicOr on next (the atomics bound the
   // top-down rate at ~40 G edges/s on MI355X).
   uint8_t* next_bytes = nullptr;
-  // List mode (small levels, multi-rank): candidate v is appended to its
+  // List mode (host loop; small levels, multi-rank): candidate v is appended to its
   // owner's list lists[o * (list_cap + 1) + 1 + k]; slot 0 of each list is its
   // count (wave-aggregated atomics, at most nranks per wave instruction).
   // list_cap >= global frontier edges guarantees no overflow.
@@ -650,8 +663,7 @@ struct TdArgs {
   // update_frontier(level_direct) derives the new frontier from it, nothing to
   // clear afterwards.
   uint8_t* level_direct = nullptr;
-  lvl_t new_level = 0;
-  uint8_t narrow_base = 0;  // (level_direct stores narrow_base + new_level)
+  LevelOut out;  // (level_direct stores out.byte())
   // Levels of at least td_hub_min_edges frontier edges read g.td_col and test
   // hub targets in an LDS copy of td_hub_vis (visited bits of the top-down
   // hubs, this level's snapshot: hub_visited); not with owner lists.
@@ -679,19 +691,15 @@ struct TdArgs {
   // Launch 1024-thread workgroups when the grid has fewer blocks than this.
   int64_t wide_below_blocks = 0;
   // Device loop: q / m come from dev_stats[0..1], bits vs bytes and the
-  // visited pre-check from ctrl; the fixed grid loops over the edge blocks.
-  const LevelCtrl* ctrl = nullptr;
+  // visited pre-check from guard.ctrl; the fixed grid loops over the edge
+  // blocks.  (Dense chains only: never with `lists`.)
+  ChainGuard guard;
   const int64_t* dev_stats = nullptr;
   int64_t grid = 0;
   int64_t grid_filter = 0;  // ... for the hub-filter variant (0: grid)
   // Device loop, work list handed over by a sparse level (no compaction ran):
-  // zero the input vertices' words of clear_frontier (clear_qv: entry -> row).
-  const vid_t* clear_qv = nullptr;
+  // zero the input vertices' (in.qv) words of clear_frontier.
   word_t* clear_frontier = nullptr;
-  // Device loop, several ranks, list form (`lists` set): live only while the
-  // global frontier edges ctrl->m_f <= max_mf (= list_cap: no list can
-  // overflow, every rank decides alike); else a no-op the host re-enqueues.
-  int64_t max_mf = 0;
   // Split level (one rank, level_direct): this launch runs part split_i of
   // split_k equal runs of the level's edge blocks; between parts
   // refresh_visited ORs the vertices claimed so far into `visited`, so a
@@ -700,16 +708,13 @@ struct TdArgs {
 };
 
 // A split top-down level (TdArgs::split_k): visited |= the vertices whose level
-// byte is narrow_base + new_level (claimed by the parts so far).  words:
-// visited words (level8 holds 64 x words bytes).
+// byte is out.byte() (claimed by the parts so far).  words: visited words
+// (out.level8 holds 64 x words bytes).
 struct RefreshArgs {
-  const uint8_t* level8 = nullptr;
-  uint8_t narrow_base = 0;
-  lvl_t new_level = 0;
+  LevelOut out;
   word_t* visited = nullptr;
   int64_t words = 0;
-  const LevelCtrl* ctrl = nullptr;
-  int64_t max_mf = 0;  // chain predicate, as TdArgs::max_mf
+  ChainGuard guard;
 };
 
 // Received candidate lists (nranks lists of list_cap + 1 words, count first)
@@ -721,11 +726,6 @@ struct ListScatterArgs {
   int64_t lo = 0;
   word_t* cand = nullptr;
   int64_t words = 0;  // words of cand (bounds check of the checked build; 0: unchecked)
-  // Device loop: the send lists' counts to zero once the exchange has read
-  // them (the next list-form chain appends from zero), and the chain guard.
-  vid_t* reset_lists = nullptr;
-  const LevelCtrl* ctrl = nullptr;
-  int64_t max_mf = 0;
 };
 
 // next[w] |= bits of bytes[64 w .. 64 w + 63]; bytes cleared (multi-rank
@@ -734,10 +734,10 @@ struct PackArgs {
   uint8_t* bytes = nullptr;
   word_t* next = nullptr;
   int64_t words = 0;
-  // device loop: runs only on a byte-map top-down level (ctrl->bytes) --
-  // or, with `flag`, on a live bottom-up level whose *flag is set (the
-  // several-rank hub cut's remote claims, BuArgs::cut_bytes)
-  const LevelCtrl* ctrl = nullptr;
+  // device loop: runs only on a live chain, and only on a byte-map top-down
+  // level (guard.ctrl->bytes) -- or, with `flag`, when *flag is set (a
+  // bottom-up chain: the several-rank hub cut's remote claims, BuArgs::cut_bytes)
+  ChainGuard guard;
   const int* flag = nullptr;
   // words [skip_begin, skip_end) are left alone (the hub cut: this rank's own
   // slice, whose claims never go through the byte map)
@@ -766,10 +766,7 @@ struct BuArgs {
   word_t* visited = nullptr;         // owned slice
   const word_t* frontier = nullptr;  // current frontier, global
   word_t* new_frontier = nullptr;    // owned slice of the next frontier (fully overwritten)
-  lvl_t* level = nullptr;
-  uint8_t* level8 = nullptr;         // narrow levels (see InitRunArgs)
-  uint8_t narrow_base = 0;             // narrow level bytes of this run: base + level (kNarrowEpochs)
-  lvl_t new_level = 0;
+  LevelOut out;
   int64_t words = 0;
   int lane_limit = 32;               // neighbours scanned per lane before wave cooperation
   bool follow_up = false;            // the previous level was bottom-up too (launch shape)
@@ -778,7 +775,7 @@ struct BuArgs {
   // (follow_up, whole_units and small_waves shape shards with packed records; without them: 16 words per wave, queued scans)
   int64_t* unit_cnt = nullptr;
   int64_t* unit_deg = nullptr;
-  const LevelCtrl* ctrl = nullptr;   // device loop: runs only when ctrl->dir == 'B'
+  ChainGuard guard;
   // One rank, device loop: the level's totals and finish (ScanArgs: stats,
   // direction decision, record, mailbox) run in the bottom-up kernel's
   // last-arriving workgroup instead of a scan launch: workgroup g stores its
@@ -795,7 +792,7 @@ struct BuArgs {
   LevelFinishArgs fin;
   // Hub-cut level (one rank, narrow levels, hub kernels with packed records,
   // cut_edges > 0; bu_cut_prep before it): when the level's frontier edges
-  // outside the hubs -- ctrl->m_f minus the frontier hubs' degrees -- are at
+  // outside the hubs -- guard.ctrl->m_f minus the frontier hubs' degrees -- are at
   // most cut_edges, hub_gather sets *cut_flag and bu_cut_prep writes the level
   // byte of the non-hub frontier vertices' unvisited neighbours (top-down);
   // every row scan of the level then stops at its first non-hub neighbour (a
@@ -829,12 +826,12 @@ struct BuArgs {
 
 // out bit h = visited bit of g.td_hub_vertex[h] (visited global): the
 // snapshot a top-down level filters hub targets with; device loop: runs only
-// when ctrl->dir == 'T' (and ctrl->m_f >= min_edges).
+// on a live chain of a level of at least min_edges frontier edges.
 struct HubVisitedArgs {
   ShardView g;
   const word_t* visited = nullptr;
   word_t* out = nullptr;
-  const LevelCtrl* ctrl = nullptr;
+  ChainGuard guard;
   int64_t min_edges = 0;
   double vis_frac = 0.0;  // as TdArgs::td_hub_vis_frac
 };
@@ -867,34 +864,29 @@ struct UnvisArgs {
   uint64_t mult = 0;
   word_t* out = nullptr;            // kUnvisWords
   uint32_t* pop = nullptr;          // kUnvisChunks: set bits per 64-word chunk
-  const LevelCtrl* ctrl = nullptr;
-  int64_t max_mf = 0;               // chain predicate, as TdArgs::max_mf
+  ChainGuard guard;
 };
 
-// level8[td_hub_vertex[h]] = narrow_base + new_level
-// for every h with mark[h] != 0, which is cleared: td_expand's hub claims
-// (TdArgs::td_hub_mark).  mark holds kTdMaxHubs bytes.
+// out.level8[td_hub_vertex[h]] = out.byte() for every h with mark[h] != 0,
+// which is cleared: td_expand's hub claims (TdArgs::td_hub_mark).  mark holds
+// kTdMaxHubs bytes.
 struct HubApplyArgs {
   ShardView g;
   uint8_t* mark = nullptr;
-  uint8_t* level8 = nullptr;
-  uint8_t narrow_base = 0;
-  lvl_t new_level = 0;
-  const LevelCtrl* ctrl = nullptr;
-  int64_t max_mf = 0;  // chain predicate, as TdArgs::max_mf
+  LevelOut out;
+  ChainGuard guard;
 };
 
 // hub_gather copies (visited merge, pushed slices) with at most this many
 // workgroups (the hub-cut part sums are sized for it)
 constexpr int kHgCopyGrid = 512;
 
-// hub_front bit h = frontier bit of g.hub_vertex[h] (frontier global); in the
-// device loop only when ctrl->dir == 'B'.
+// hub_front bit h = frontier bit of g.hub_vertex[h] (frontier global).
 struct HubGatherArgs {
   ShardView g;
   const word_t* frontier = nullptr;
   word_t* hub_front = nullptr;  // ceil(nhubs / 64) words
-  const LevelCtrl* ctrl = nullptr;
+  ChainGuard guard;
   // several ranks: visited[0, words) |= frontier (the all-gathered remote
   // slices into the replicated visited bitmap) in the same launch
   word_t* visited = nullptr;

@@ -218,17 +218,15 @@ struct EngineOptions {
   // cost what they save)
   int64_t td_hub_edges = int64_t(1) << 24;
   // ... once the visited vertices hold this fraction of the adjacency.
-  // Without hub marks (td_hub_mark) 0, i.e. also the earlier big levels, was
-  // slower (58.9 against 63.5 GTEPS: decoding unvisited hubs costs a
-  // dependent load); with them 0 is faster (69.0 against 65.9).
+  // Without hub marks (TdArgs::td_hub_mark: direct-level top-down claims a
+  // hub target as one byte of an L2-resident 128 KiB array, hub_apply turns
+  // the marks into level bytes after the expansion) 0, i.e. also the earlier
+  // big levels, was slower (58.9 against 63.5 GTEPS: decoding unvisited hubs
+  // costs a dependent load); with them 0 is faster (69.0 against 65.9).
   double td_hub_vis_frac = 0.0;
   // ... only on graphs whose top-down hubs hold at least this share of the
   // adjacency entries (DeviceGraph::td_hub_share)
   static constexpr double td_hub_min_share = 0.0;
-  // Direct-level top-down: hub targets claimed as one byte per hub (an
-  // L2-resident 128 KiB array) and turned into level bytes after the
-  // expansion (TdArgs::td_hub_mark, hub_apply).
-  static constexpr bool td_hub_mark = true;
   // Byte-map levels skip the visited pre-check while the visited vertices
   // hold less than this fraction of all adjacency entries.
   double td_check_visited_min = 0.02;
@@ -241,20 +239,15 @@ struct EngineOptions {
   // switch this off to exercise the list path on small graphs).
   bool sparse_size_check = true;
   bool phase_timing = false;  // per-level device timing (adds events)
-  // One rank, td/bu/do modes: device-driven level loop (LevelCtrl): the host
-  // enqueues the next level before the current one finishes.
+  // td/bu/do modes: device-driven level loop (LevelCtrl): the host enqueues
+  // the next level before the current one finishes.  With several ranks each
+  // level's chain carries its collectives (frontier all-gather, candidate
+  // all-to-all, totals all-reduce), enqueued ahead like the kernels;
+  // level_finish decides on the reduced totals.
   bool device_loop = true;
-  // ... also with several ranks: each level's chain carries its collectives
-  // (frontier all-gather, candidate all-to-all, totals all-reduce), enqueued
-  // ahead like the kernels; level_finish decides on the reduced totals.
-  static constexpr bool device_loop_ranks = true;
   // ... enqueueing each level with an extrapolated direction prediction (else:
   // the previous level's direction, one more level ahead).
   bool device_loop_predict = true;
-  // Host loop (several ranks, or device_loop off): read each level's totals
-  // through a device-mapped mailbox the host spins on, instead of a D2H copy
-  // plus a stream synchronisation.
-  static constexpr bool stats_mailbox = true;
   // Device loop: top-down levels whose frontier is predicted to have at most
   // this many edges run as one sparse kernel (TdSparseArgs: direct claims, work list
   // handed to the next level) instead of compact + td_expand + update + scan;
@@ -289,25 +282,6 @@ struct EngineOptions {
   // (TdSparseArgs::from_bits: one kernel after a clear of its output bitmap,
   // instead of scan_units + compact + td_sparse).
   bool td_sparse_bits = true;
-  // Device loop: a bottom-up level's unit scan (totals; one rank: direction
-  // decision, mailbox stamp) runs in the bottom-up kernel's last-arriving
-  // workgroup instead of a kernel of its own.
-  static constexpr bool bu_fused_scan = true;
-  // Device loop: a dense top-down level's update finishes the
-  // level itself (as bu_fused_scan; per-workgroup totals slots, 512
-  // workgroups striding over the units with one ticket, the full grid with
-  // td_group_ticket): no scan launch unless a compaction follows.
-  // RMAT-26 1344 / 1341 -> 1363 / 1353 GTEPS; top-down only equal within noise.
-  // (A first version with one workgroup per 4 units and totals atomics on
-  // one address: level 1 of RMAT-26 38 -> 117 us.)
-  static constexpr bool td_fused_finish = true;
-  // ... and on graphs of at most kFoldScanUnits 4096-vertex units (2^25
-  // vertices) its last workgroup also scans the unit prefixes the next
-  // compaction reads (UpdateArgs::fold_scan): one launch less per dense level
-  static constexpr bool fold_scan = true;
-  // ... with a two-level ticket (UpdateArgs::group_ticket): the update runs
-  // a full grid (up to kMaxFusedGrid workgroups) instead of kMaxFusedGrid / 8.
-  static constexpr bool td_group_ticket = true;
   // Device loop, several ranks: sparse top-down levels (td_sparse with owner
   // lists, the lists exchanged count-sized, td_sparse_apply on the owners)
   // for levels predicted at <= xsparse_edges global frontier edges; such a
@@ -360,14 +334,6 @@ struct EngineOptions {
   // the peer windows ship their lengths), a chain's lists hold
   // list_cap_factor x the predicted edges (a power of two >= 1024)
   double list_cap_factor = 4.0;
-  // Sparse chains on a transport with a direct exchange (peer windows,
-  // Comm::direct_lists): td_sparse stores remote claims straight into their
-  // owners' windows and td_sparse_apply waits for the flags -- no exchange
-  // launch in between
-  static constexpr bool direct_lists = true;
-  // ... and their level's end folded into td_sparse_apply's last workgroup
-  // (Comm::direct_level_end) when it gathers no frontier
-  static constexpr bool direct_level_end = true;
   // Several ranks, a level whose frontier is all-gathered for a bottom-up
   // level next (graphs with hubs): the producing kernels push their output
   // words straight into the peers' windows (Comm::direct_frontier) and the
@@ -380,10 +346,6 @@ struct EngineOptions {
   // widened to 32 bits when read; a traversal deeper than kNarrowMaxLevel is
   // rerun with 32-bit levels (and later runs keep them).
   bool narrow_levels = true;
-  // Narrow level bytes stored as base + level with the base cycling through
-  // kNarrowEpochs values, so only one run in kNarrowEpochs fills the byte
-  // array (the others read the earlier epochs' bytes as unreached).
-  static constexpr bool narrow_epochs = true;
   // Take the multi-rank exchange path (alltoall / allgather / alltoallv) even
   // with one rank: lets a 1-rank RCCL communicator exercise every collective
   // call on a single GPU (tests).
@@ -559,6 +521,11 @@ class Engine {
   void begin_run_scratch();
   InitRunArgs init_args(int64_t source, word_t* seed_frontier, LevelCtrl* ctrl, const LevelCtrl& ctrl_init,
                         LevelMailbox* mailbox);
+  // Where a level's new vertices get new_level: the narrow array on a narrow
+  // run (the one place that decides it), else the 32-bit one.
+  LevelOut level_out(lvl_t new_level) const {
+    return {level_.data(), run_narrow_ ? level8_.data() : nullptr, narrow_base_, new_level};
+  }
   bool scratch_dirty_ = true;  // cand / next / byte map may hold stale bits
   bool frontier_clean_ = false;  // the owned frontier slices are zero (InitRunArgs::frontier_clean)
   void alloc_ref_state();
@@ -582,7 +549,7 @@ class Engine {
   DBuf<int64_t> td_tot_;  // fused top-down finish: the level's totals (UpdateArgs::tot)
   DBuf<uint8_t> td_hub_mark_;  // TdArgs::td_hub_mark (kTdMaxHubs bytes; zero between levels)
   bool level8_filled_ = false;        // level8_ reads unreached for the current run without a fill
-  uint8_t narrow_base_ = 0;           // the current run's level byte base (narrow_epochs)
+  uint8_t narrow_base_ = 0;           // the current run's level byte base (kNarrowEpochs)
   int64_t narrow_run_ = 0;            // narrow runs since level8_ was allocated
   bool narrow_failed_ = false;        // a traversal overflowed the narrow levels
   bool run_narrow_ = false;           // the current run writes level8_

@@ -77,19 +77,19 @@ __global__ __launch_bounds__(kBlock) void init_run_kernel(InitRunArgs a) {
   const int64_t t0 = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const int64_t rows = a.g.rows;
   const int64_t src = a.src_local;
-  if (a.level8 && a.level8_filled) {
+  if (a.out.level8 && a.level8_filled) {
     // already reads unreached for this run (prefilled, or an earlier epoch's
     // bytes): the source's byte only
-    if (src >= 0 && t0 == 0) a.level8[src] = a.narrow_base;
-  } else if (a.level8) {
+    if (src >= 0 && t0 == 0) a.out.level8[src] = a.out.narrow_base;
+  } else if (a.out.level8) {
     // narrow levels: rows / 16 uint4 stores of 0xFF (+ tail), the source's byte after
-    const int64_t n16 = (reinterpret_cast<uintptr_t>(a.level8) & 15u) == 0 ? rows / 16 : 0;
-    uint4* l16 = reinterpret_cast<uint4*>(a.level8);
+    const int64_t n16 = (reinterpret_cast<uintptr_t>(a.out.level8) & 15u) == 0 ? rows / 16 : 0;
+    uint4* l16 = reinterpret_cast<uint4*>(a.out.level8);
     for (int64_t i = t0; i < n16; i += stride) {
       uint4 v = make_uint4(~0u, ~0u, ~0u, ~0u);
       if (src >= 0 && (src >> 4) == i) {
         const unsigned clear = ~(0xFFu << (8 * (src & 3)));
-        const unsigned set = static_cast<unsigned>(a.narrow_base) << (8 * (src & 3));
+        const unsigned set = static_cast<unsigned>(a.out.narrow_base) << (8 * (src & 3));
         const int word = static_cast<int>((src >> 2) & 3);
         if (word == 0) v.x = (v.x & clear) | set;
         else if (word == 1) v.y = (v.y & clear) | set;
@@ -98,11 +98,11 @@ __global__ __launch_bounds__(kBlock) void init_run_kernel(InitRunArgs a) {
       }
       l16[i] = v;
     }
-    for (int64_t i = n16 * 16 + t0; i < rows; i += stride) a.level8[i] = i == src ? a.narrow_base : kNarrowUnreached;
+    for (int64_t i = n16 * 16 + t0; i < rows; i += stride) a.out.level8[i] = i == src ? a.out.narrow_base : kNarrowUnreached;
   } else {
     // level: rows / 4 int4 stores (+ tail)
-    const int64_t n4 = (reinterpret_cast<uintptr_t>(a.level) & 15u) == 0 ? rows / 4 : 0;
-    int4* l4 = reinterpret_cast<int4*>(a.level);
+    const int64_t n4 = (reinterpret_cast<uintptr_t>(a.out.level) & 15u) == 0 ? rows / 4 : 0;
+    int4* l4 = reinterpret_cast<int4*>(a.out.level);
     for (int64_t i = t0; i < n4; i += stride) {
       int4 v = make_int4(kUnreached, kUnreached, kUnreached, kUnreached);
       if (src >= 0 && (src >> 2) == i) {
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void init_run_kernel(InitRunArgs a) {
       }
       l4[i] = v;
     }
-    for (int64_t i = n4 * 4 + t0; i < rows; i += stride) a.level[i] = i == src ? 0 : kUnreached;
+    for (int64_t i = n4 * 4 + t0; i < rows; i += stride) a.out.level[i] = i == src ? 0 : kUnreached;
   }
   // (the source's visited bit: in every rank's replicated bitmap when the
   // global id is known -- a seed without collective -- else on its owner)
@@ -132,9 +132,9 @@ __global__ __launch_bounds__(kBlock) void init_run_kernel(InitRunArgs a) {
   if (a.frontier_clear && !a.frontier_clean)
     for (int64_t w = t0; w < a.words; w += stride) a.frontier_clear[w] = 0ull;
   // the seed's work-list entry: edge blocks [0, ceil(d / EPB)) all start in it
-  if (a.blk_vstart && src >= 0) {
+  if (a.wl.blk_vstart && src >= 0) {
     const eid_t d = a.g.row_off[src + 1] - a.g.row_off[src];
-    for (int64_t b = t0; b * kTdEdgesPerBlock < d; b += stride) a.blk_vstart[b] = 0;
+    for (int64_t b = t0; b * kTdEdgesPerBlock < d; b += stride) a.wl.blk_vstart[b] = 0;
   }
   if (t0 != 0) return;
   int64_t cnt = 0, deg = 0;
@@ -152,11 +152,11 @@ __global__ __launch_bounds__(kBlock) void init_run_kernel(InitRunArgs a) {
   }
   a.stats[0] = a.stats[2] = cnt;
   a.stats[1] = a.stats[3] = deg;
-  a.qscan[cnt] = deg;
-  if (cnt && a.qbase) {
-    a.qscan[0] = 0;
-    a.qbase[0] = a.g.row_off[src];
-    a.qv[0] = static_cast<vid_t>(src);
+  a.wl.qscan[cnt] = deg;
+  if (cnt && a.wl.qbase) {
+    a.wl.qscan[0] = 0;
+    a.wl.qbase[0] = a.g.row_off[src];
+    a.wl.qv[0] = static_cast<vid_t>(src);
   }
   if (a.ctrl) {
     // the seed's global totals: this rank's own, or (several ranks) from the
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void init_run_kernel(InitRunArgs a) {
       a.stats[3] = gd;
     }
     LevelCtrl c = a.ctrl_init;
-    finish_level(a.ctrl, c, gc, gd, true, nullptr, a.mailbox, -1);
+    finish_level(LevelStamp{a.ctrl, nullptr, a.mailbox, -1, true}, c, gc, gd);
   }
 }
 
@@ -350,7 +350,7 @@ __device__ __forceinline__ void update_unit(const UpdateArgs& a, int64_t unit, b
   if (lane < kWords && wl < a.words) {
     word_t c = 0;
     if (use_bytes && a.level_direct) {
-      c = gather_level_bits(a.level_direct + wl * 64, static_cast<uint8_t>(a.narrow_base + a.new_level));
+      c = gather_level_bits(a.level_direct + wl * 64, a.out.byte());
     } else if (use_bytes) {
       c = gather_byte_bits(a.cand_bytes + wl * 64);
     } else {
@@ -379,7 +379,7 @@ __device__ __forceinline__ void update_unit(const UpdateArgs& a, int64_t unit, b
     const int pos = wave_set_position(nb, incl, idx);
     if (idx < total) {
       const int64_t v = w0 * 64 + pos;
-      if (!(use_bytes && a.level_direct)) store_level(a.level, a.level8, v, a.new_level, a.narrow_base);
+      if (!(use_bytes && a.level_direct)) a.out.store(v);
       const eid_t d = ro[v + 1] - ro[v];
       if (d > 0) {
         cnt += 1;
@@ -421,16 +421,14 @@ template <bool kSplit, bool kRanks>
 __global__ __launch_bounds__(kBlock) void update_kernel(UpdateArgs a) {
   __shared__ uint64_t s_x[kRanks ? 2 * kern::kMaxPeers : 1];  // (the folded level end's cells)
   bool use_bytes = a.cand_bytes != nullptr;
-  if (a.ctrl) {
-    if (!chain_live(*a.ctrl, 'T', a.max_mf)) {
-      // a folded level end is a collective: it runs on a no-op chain too
-      if constexpr (kRanks)
-        if (a.end.active && blockIdx.x == 0)
-          direct_level_end(a.end, a.scan.stats[2], a.scan.stats[3], a.scan.stats, a.fin, s_x);
-      return;
-    }
-    use_bytes = use_bytes && a.ctrl->bytes != 0;
+  if (!a.guard.live()) {
+    // a folded level end is a collective: it runs on a no-op chain too
+    if constexpr (kRanks)
+      if (a.end.active && blockIdx.x == 0)
+        direct_level_end(a.end, a.scan.stats[2], a.scan.stats[3], a.scan.stats, a.fin, s_x);
+    return;
   }
+  if (a.guard.ctrl) use_bytes = use_bytes && a.guard.ctrl->bytes != 0;
   const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));  // (wave-uniform)
   const int64_t nunits = (a.words + kUnitWords - 1) / kUnitWords;
   __shared__ long long s_pc[kUnitsPerBlock], s_pd[kUnitsPerBlock];
@@ -494,21 +492,15 @@ __global__ __launch_bounds__(kBlock) void update_kernel(UpdateArgs a) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.tot + 2 * blockIdx.x + 1),
                        static_cast<unsigned long long>(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (a.group_ticket) {
-      // the group's last workgroup sums the group (below), then takes the
-      // level ticket
-      const unsigned grp = blockIdx.x / kFusedGroup;
-      const unsigned gsz = min(static_cast<unsigned>(kFusedGroup), gridDim.x - grp * kFusedGroup);
-      const unsigned prev = atomicAdd(a.group_ticket + grp * kBuQueueStride, 1u);
-      s_last = prev == gsz - 1;
-      if (s_last) {
-        atomicExch(a.group_ticket + grp * kBuQueueStride, 0u);
-        last_arriver_acquire();
-      }
-    } else {
-      const unsigned prev = atomicAdd(a.scan.ticket, 1u);
-      s_last = prev == gridDim.x - 1;
-      if (s_last) last_arriver_acquire();
+    // the group's last workgroup sums the group (below), then takes the
+    // level ticket
+    const unsigned grp = blockIdx.x / kFusedGroup;
+    const unsigned gsz = min(static_cast<unsigned>(kFusedGroup), gridDim.x - grp * kFusedGroup);
+    const unsigned prev = atomicAdd(a.group_ticket + grp * kBuQueueStride, 1u);
+    s_last = prev == gsz - 1;
+    if (s_last) {
+      atomicExch(a.group_ticket + grp * kBuQueueStride, 0u);
+      last_arriver_acquire();
     }
   }
   __syncthreads();
@@ -525,32 +517,28 @@ __global__ __launch_bounds__(kBlock) void update_kernel(UpdateArgs a) {
     }
   };
   long long c = 0, d = 0;
-  if (a.group_ticket) {
-    // group total (kFusedGroup slots: the first wave), then the level ticket
-    const unsigned grp = blockIdx.x / kFusedGroup;
-    const unsigned ngroups = (gridDim.x + kFusedGroup - 1) / kFusedGroup;
-    if (wv == 0) {
-      slot_sum(a.tot, grp * kFusedGroup, min(static_cast<unsigned>(kFusedGroup), gridDim.x - grp * kFusedGroup), c, d);
-      c = wave_sum(c);
-      d = wave_sum(d);
-      if (lane_id() == 0) {
-        int64_t* gt = a.tot + 2 * kMaxFusedGrid;
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(gt + 2 * grp), static_cast<unsigned long long>(c),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(gt + 2 * grp + 1), static_cast<unsigned long long>(d),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned prev = atomicAdd(a.scan.ticket, 1u);
-        s_level_last = prev == ngroups - 1;
-        if (s_level_last) last_arriver_acquire();
-      }
+  // group total (kFusedGroup slots: the first wave), then the level ticket
+  const unsigned grp = blockIdx.x / kFusedGroup;
+  const unsigned ngroups = (gridDim.x + kFusedGroup - 1) / kFusedGroup;
+  if (wv == 0) {
+    slot_sum(a.tot, grp * kFusedGroup, min(static_cast<unsigned>(kFusedGroup), gridDim.x - grp * kFusedGroup), c, d);
+    c = wave_sum(c);
+    d = wave_sum(d);
+    if (lane_id() == 0) {
+      int64_t* gt = a.tot + 2 * kMaxFusedGrid;
+      __hip_atomic_store(reinterpret_cast<unsigned long long*>(gt + 2 * grp), static_cast<unsigned long long>(c),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(reinterpret_cast<unsigned long long*>(gt + 2 * grp + 1), static_cast<unsigned long long>(d),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned prev = atomicAdd(a.scan.ticket, 1u);
+      s_level_last = prev == ngroups - 1;
+      if (s_level_last) last_arriver_acquire();
     }
-    __syncthreads();
-    if (!s_level_last) return;
-    slot_sum(a.tot + 2 * kMaxFusedGrid, 0, ngroups, c, d);
-  } else {
-    slot_sum(a.tot, 0, gridDim.x, c, d);
   }
+  __syncthreads();
+  if (!s_level_last) return;
+  slot_sum(a.tot + 2 * kMaxFusedGrid, 0, ngroups, c, d);
   c = wave_sum(c);
   d = wave_sum(d);
   __syncthreads();  // (s_c / s_d reused)
@@ -585,7 +573,7 @@ __global__ __launch_bounds__(kBlock) void update_kernel(UpdateArgs a) {
 // sums the units, thread 0 finishes.
 __global__ __launch_bounds__(kScanChunk) void totals_finish_kernel(ScanArgs a) {
   __shared__ long long s_c[kScanChunk / kWave], s_d[kScanChunk / kWave];
-  if (a.ctrl && !chain_live(*a.ctrl, a.expect_dir, a.expect_cap)) return;
+  if (!a.guard.live()) return;
   long long c = 0, d = 0;
   for (int64_t u = threadIdx.x; u < a.nunits; u += kScanChunk) {
     c += a.unit_cnt[u];
@@ -620,7 +608,7 @@ __global__ __launch_bounds__(kScanChunk) void scan_units_kernel(ScanArgs a) {
   __shared__ long long s_c[kScanChunk / kWave], s_d[kScanChunk / kWave];
   __shared__ int s_last;
   // uniform: no block takes a ticket
-  if (a.ctrl && !chain_live(*a.ctrl, a.expect_dir, a.expect_cap)) return;
+  if (!a.guard.live()) return;
   const int t = threadIdx.x;
   const int lane = lane_id();
   const int wv = t >> 6;
@@ -710,8 +698,8 @@ __global__ __launch_bounds__(kScanChunk) void scan_units_kernel(ScanArgs a) {
 // cache hits) writes -- twice the passes, a quarter of the steps each.
 template <bool kSplit>
 __global__ __launch_bounds__(kBlock) void compact_kernel(CompactArgs a) {
-  if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
-  stamp_level_start(a.ctrl);
+  if (!a.guard.live()) return;
+  stamp_level_start(a.guard.ctrl);
   constexpr int kWords = kSplit ? kWaveWords : kUnitWords;
   const int lane = lane_id();
   const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));  // (wave-uniform)
@@ -772,11 +760,11 @@ __global__ __launch_bounds__(kBlock) void compact_kernel(CompactArgs a) {
     const long long qs = off + incl - d;
     DBFS_DCHECK(!take || p < a.g.rows, 1, p);
     if (take) {
-      a.qscan[p] = qs;
-      a.qbase[p] = rs - qs;
-      if (a.qv) a.qv[p] = static_cast<vid_t>(w0 * 64 + vpos);
+      a.wl.qscan[p] = qs;
+      a.wl.qbase[p] = rs - qs;
+      if (a.wl.qv) a.wl.qv[p] = static_cast<vid_t>(w0 * 64 + vpos);
     }
-    wave_fill_blocks(a.blk_vstart, take, qs, d, p);
+    wave_fill_blocks(a.wl.blk_vstart, take, qs, d, p);
     pos += __popcll(tm);
     off += readlane_i64(incl, kWave - 1);
   }
@@ -794,11 +782,7 @@ __global__ __launch_bounds__(kBlock) void widen_levels_kernel(const uint8_t* __r
 
 // Received owner lists -> candidate bits of the owned slice.
 __global__ __launch_bounds__(kBlock) void list_scatter_kernel(ListScatterArgs a) {
-  if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
   const int r = blockIdx.y;
-  // the send lists were read by the exchange (stream-ordered before this
-  // kernel): their counts restart from zero for the next list-form chain
-  if (a.reset_lists && blockIdx.x == 0 && threadIdx.x == 0) a.reset_lists[static_cast<int64_t>(r) * (a.list_cap + 1)] = 0;
   const vid_t* list = a.lists + static_cast<int64_t>(r) * (a.list_cap + 1);
   const int64_t n = list[0];
   DBFS_DCHECK(n <= a.list_cap, 5, n);
@@ -812,8 +796,7 @@ __global__ __launch_bounds__(kBlock) void list_scatter_kernel(ListScatterArgs a)
 
 // Byte map -> bitmap for the multi-rank exchange (words of 64 vertices).
 __global__ __launch_bounds__(kBlock) void pack_bytes_kernel(PackArgs a) {
-  if (a.ctrl && (a.ctrl->done || (a.flag ? a.ctrl->dir != 'B' || !*a.flag : a.ctrl->dir != 'T' || !a.ctrl->bytes)))
-    return;
+  if (!a.guard.live() || (a.guard.ctrl && !(a.flag ? *a.flag : a.guard.ctrl->bytes))) return;
   int64_t w = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (w >= a.skip_begin) w += a.skip_end - a.skip_begin;  // (the grid covers the other words only)
   if (w >= a.words) return;
@@ -867,11 +850,11 @@ __global__ __launch_bounds__(kBlock) void copy_pieces_kernel(Backend::CopyPieces
 // RefreshArgs (a split top-down level): the claims of the parts so far into
 // visited -- a word per thread, its 64 level bytes in four 16-byte loads.
 __global__ __launch_bounds__(kBlock) void refresh_visited_kernel(RefreshArgs a) {
-  if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
-  const uint8_t lv = static_cast<uint8_t>(a.narrow_base + a.new_level);
+  if (!a.guard.live()) return;
+  const uint8_t lv = a.out.byte();
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
   for (int64_t w = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; w < a.words; w += stride) {
-    const word_t m = gather_level_bits(a.level8 + w * 64, lv);
+    const word_t m = gather_level_bits(a.out.level8 + w * 64, lv);
     if (m) a.visited[w] |= m;
   }
 }
@@ -905,17 +888,16 @@ void publish_stats(const int64_t* stats, StatsMailbox* mb, int64_t seq, hipStrea
 }
 
 void update_frontier(const UpdateArgs& a, hipStream_t st) {
-  DBFS_CHECK(!a.end.active || (a.fuse_scan && a.ctrl && a.scan.stats), "update: a folded level end needs the fused finish");
+  DBFS_CHECK(!a.end.active || (a.fuse_scan && a.guard.ctrl && a.scan.stats), "update: a folded level end needs the fused finish");
   if (a.words <= 0) return;
   const int64_t nunits = (a.words + kUnitWords - 1) / kUnitWords;
   DBFS_CHECK(!a.fold_scan || (a.fuse_scan && a.scan.nunits == nunits && nunits <= kFoldScanUnits),
              "update: fold_scan needs the fused finish over at most kFoldScanUnits units");
   const bool split = nunits < kUpdateSplitUnits;
   const int64_t per = split ? kUnitWords : kUnitWords * kUnitsPerBlock;
-  // fused finish: at most kMaxFusedGrid / 8 workgroups striding over the units
-  // with one ticket; up to kMaxFusedGrid with the two-level ticket
-  const unsigned grid = a.fuse_scan ? grid_for(a.words, per, a.group_ticket ? kMaxFusedGrid : kMaxFusedGrid / 8)
-                                    : grid_for(a.words, per);
+  DBFS_CHECK(!a.fuse_scan || a.group_ticket, "update: the fused finish needs the group tickets");
+  // fused finish: at most kMaxFusedGrid workgroups striding over the units
+  const unsigned grid = a.fuse_scan ? grid_for(a.words, per, kMaxFusedGrid) : grid_for(a.words, per);
   const bool ranks = a.push || a.zero_next || a.end.active;
   if (split && ranks) update_kernel<true, true><<<grid, kBlock, 0, st>>>(a);
   else if (split) update_kernel<true, false><<<grid, kBlock, 0, st>>>(a);

@@ -228,13 +228,13 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
   word_t pw = 0;
   if constexpr (kCut) {
     if (cut && lane < nw) {
-      const uint8_t* src = kCut == kCutClaims ? a.cut_claim : a.level8;
+      const uint8_t* src = kCut == kCutClaims ? a.cut_claim : a.out.level8;
       const uint4* lb = reinterpret_cast<const uint4*>(src + (w0 + lane) * 64);
       const uint64_t cur = kCut == kCutClaims ? 0ull
                                        : 0x0101010101010101ull *
-                                             static_cast<uint8_t>(a.narrow_base + (a.new_level <= kNarrowMaxLevel
-                                                                                       ? a.new_level
-                                                                                       : kNarrowMaxLevel + 1));
+                                             static_cast<uint8_t>(a.out.narrow_base + (a.out.new_level <= kNarrowMaxLevel
+                                                                                           ? a.out.new_level
+                                                                                           : kNarrowMaxLevel + 1));
       uint4 q[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) q[k] = lb[k];
@@ -270,7 +270,7 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
         for (word_t m = pw; m; m &= m - 1) {
           const int64_t v = (w0 + lane) * 64 + __builtin_ctzll(m);
           d += static_cast<long long>(a.g.row_off[v + 1] - a.g.row_off[v]);
-          if constexpr (kCut == kCutClaims) a.level[v] = a.new_level;
+          if constexpr (kCut == kCutClaims) a.out.level[v] = a.out.new_level;
           ++c;
         }
         cnt += c;
@@ -403,7 +403,7 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
   }
   auto settle = [&](bool f, int l, eid_t r0, eid_t r1) {
     if (f) {
-      store_level(a.level, a.level8, w0 * 64 + l, a.new_level, a.narrow_base);
+      a.out.store(w0 * 64 + l);
       cnt32 += 1;
       deg += r1 - r0;
       __hip_atomic_fetch_or(s_res + (l >> 6), 1ull << (l & 63), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -545,8 +545,8 @@ __device__ __forceinline__ void bu_wave_compact(const BuArgs& a, int64_t w0, wor
 // Graphs without hubs: a wave per 16 words, 4 waves (one unit) per workgroup.
 __global__ __launch_bounds__(kUnitThreads) void bu_kernel(BuArgs a) {
   __shared__ word_t s_res[kUnitWaves * kWaveWords];
-  if (a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) return;
-  stamp_level_start(a.ctrl);
+  if (!a.guard.live()) return;
+  stamp_level_start(a.guard.ctrl);
   long long cnt = 0, deg = 0;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));  // (wave-uniform)
   const int64_t w0 = static_cast<int64_t>(blockIdx.x) * kUnitWords + wave * kWaveWords;
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(kThreads, 2 * kThreads / 256) void bu_hub_kernel(Bu
   __shared__ word_t s_res[(kThreads / kWave) * kUnitWords];
   __shared__ long long s_c[kThreads / kWave], s_d[kThreads / kWave];
   __shared__ unsigned long long s_q[kQ > 0 ? (kThreads / kWave) * kQ : 1];
-  if (a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) {
+  if (!a.guard.live()) {
     // a folded level end is a collective: it runs on a no-op chain too
     if constexpr (kEnd) {
       if (blockIdx.x == 0)
@@ -680,7 +680,7 @@ __global__ __launch_bounds__(kThreads, 2 * kThreads / 256) void bu_hub_kernel(Bu
   // second, plain launch that returned at once on every cut level (~4.5 us
   // of idle GPU per late-switch traversal)
   const bool cut = kCut != 0 && *a.cut_flag != 0;
-  if (!a.hub_front) stamp_level_start(a.ctrl);
+  if (!a.hub_front) stamp_level_start(a.guard.ctrl);
   const int64_t hw = (a.g.nhubs + kWordBits - 1) / kWordBits;
   stage_words<kThreads, kHubWords>(s_hub, a.hub_front, hw);
   __syncthreads();
@@ -810,8 +810,8 @@ __device__ __forceinline__ bool pulled_bit(const HubGatherArgs& a, vid_t v) {
 // workgroups -- fewer ticket arrivals)
 template <bool kCut, int kThreads, int kPer>
 __global__ __launch_bounds__(kThreads) void hub_gather_kernel(HubGatherArgs a) {
-  if (a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) return;
-  stamp_level_start(a.ctrl);
+  if (!a.guard.live()) return;
+  stamp_level_start(a.guard.ctrl);
   __shared__ long long s_d[kThreads / kWave];
   __shared__ int s_last;
   const int lane = lane_id();
@@ -884,7 +884,7 @@ __global__ __launch_bounds__(kThreads) void hub_gather_kernel(HubGatherArgs a) {
     long long hub_edges = 0;
 #pragma unroll
     for (int k = 0; k < kThreads / kWave; ++k) hub_edges += s_d[k];
-    *a.cut_flag = a.ctrl->m_f - hub_edges <= a.cut_edges ? 1 : 0;
+    *a.cut_flag = a.guard.ctrl->m_f - hub_edges <= a.cut_edges ? 1 : 0;
     *a.cut_ticket = 0u;
   }
 }
@@ -909,7 +909,7 @@ __global__ __launch_bounds__(kThreads) void hub_gather_kernel(HubGatherArgs a) {
 constexpr int kCutThreads = 1024;
 template <bool kX>
 __global__ __launch_bounds__(kCutThreads) void bu_cut_prep_kernel(BuArgs a) {
-  if ((a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) || !*a.cut_flag) return;
+  if (!a.guard.live() || !*a.cut_flag) return;
   const vid_t* __restrict__ col = a.g.col;
   const eid_t* __restrict__ ro = a.g.row_off;
   const word_t* __restrict__ fr = a.frontier + (kX ? a.cut_word_off : 0);
@@ -947,7 +947,7 @@ __global__ __launch_bounds__(kCutThreads) void bu_cut_prep_kernel(BuArgs a) {
             continue;
           }
           if (a.cut_claim) a.cut_claim[r] = 1;  // (wide levels: the bottom-up kernel writes them)
-          else store_level(nullptr, a.level8, static_cast<int64_t>(r), a.new_level, a.narrow_base);
+          else a.out.store(static_cast<int64_t>(r));
         }
       }
     }
@@ -960,7 +960,7 @@ __global__ __launch_bounds__(kCutThreads) void bu_cut_prep_kernel(BuArgs a) {
 // zeroed (cut_next: the dense top-down levels' candidate bitmap, kept zero
 // between users).
 __global__ __launch_bounds__(kBlock) void bu_cut_merge_kernel(BuArgs a) {
-  if ((a.ctrl && (a.ctrl->done || a.ctrl->dir != 'B')) || !*a.cut_flag) return;
+  if (!a.guard.live() || !*a.cut_flag) return;
   const int64_t w = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (w >= a.words) return;
   word_t c = 0;
@@ -973,7 +973,7 @@ __global__ __launch_bounds__(kBlock) void bu_cut_merge_kernel(BuArgs a) {
   for (; c; c &= c - 1) {
     const int64_t r = w * 64 + __builtin_ctzll(c);
     if (a.cut_claim) a.cut_claim[r] = 1;
-    else store_level(nullptr, a.level8, r, a.new_level, a.narrow_base);
+    else a.out.store(r);
   }
 }
 
@@ -1121,7 +1121,7 @@ void bu_step(const BuArgs& a, hipStream_t st) {
       totals_finish(a.scan, st);
       return;
     }
-    DBFS_CHECK(s.cut == 0 || (s.rec && !a.follow_up && a.cut_flag && (a.level8 || (a.cut_claim && a.level)) && a.g.hub_bits),
+    DBFS_CHECK(s.cut == 0 || (s.rec && !a.follow_up && a.cut_flag && (a.out.level8 || (a.cut_claim && a.out.level)) && a.g.hub_bits),
                "bu_step: hub-cut level without packed records / flag / claim bytes");
     bu_dispatch(a, s, st);
     return;
@@ -1132,7 +1132,7 @@ void bu_step(const BuArgs& a, hipStream_t st) {
 }
 
 void bu_cut_prep(const BuArgs& a, hipStream_t st) {
-  DBFS_CHECK(a.cut_edges > 0 && a.cut_flag && (a.level8 || a.cut_claim) && a.g.hub_bits && a.ctrl,
+  DBFS_CHECK(a.cut_edges > 0 && a.cut_flag && (a.out.level8 || a.cut_claim) && a.g.hub_bits && a.guard.ctrl,
              "bu_cut_prep: hub-cut arguments missing");
   const bool x = a.cut_bytes != nullptr;
   DBFS_CHECK(!x || (a.cut_vis && a.cut_word_off >= 0), "bu_cut_prep: several ranks' claim arguments missing");
@@ -1144,7 +1144,7 @@ void bu_cut_prep(const BuArgs& a, hipStream_t st) {
 }
 
 void bu_cut_merge(const BuArgs& a, hipStream_t st) {
-  DBFS_CHECK(a.cut_flag && a.cut_recv && a.cut_next && (a.level8 || a.cut_claim) && a.cut_nranks > 1 &&
+  DBFS_CHECK(a.cut_flag && a.cut_recv && a.cut_next && (a.out.level8 || a.cut_claim) && a.cut_nranks > 1 &&
                  a.cut_rank >= 0 && a.cut_rank < a.cut_nranks && a.words > 0,
              "bu_cut_merge: several ranks' hub-cut arguments missing");
   bu_cut_merge_kernel<<<grid_for(a.words, kBlock), kBlock, 0, st>>>(a);
@@ -1162,7 +1162,7 @@ void hub_gather(const HubGatherArgs& a, hipStream_t st) {
   if (a.visited || a.pull)
     grid = std::max(grid, grid_for(a.pull ? a.pull_words * a.pull_nranks : a.words, kHgThreads, kHgCopyGrid));
   if (a.cut_part) {
-    DBFS_CHECK(a.cut_flag && a.cut_ticket && a.ctrl, "hub_gather: the hub-cut decision needs a flag, a ticket and the level state");
+    DBFS_CHECK(a.cut_flag && a.cut_ticket && a.guard.ctrl, "hub_gather: the hub-cut decision needs a flag, a ticket and the level state");
     hub_gather_kernel<true, kHgThreads, kHgPer><<<grid, kHgThreads, 0, st>>>(a);
     return;
   }

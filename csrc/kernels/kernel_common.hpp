@@ -1,6 +1,6 @@
 // Device helpers shared by the traversal kernel files (bfs_kernels.hip:
 // level bookkeeping, td_kernels.hip: top-down, bu_kernels.hip: bottom-up):
-// the checked-build macro, level stores, last-arriver hand-offs, the scan
+// the checked-build macro, last-arriver hand-offs, the scan
 // finish, work-list block starts, the direct-exchange words and the folded
 // level end.  Everything lives in an anonymous namespace: each kernel file
 // gets its own copy (device globals such as g_check included).
@@ -56,17 +56,6 @@ __device__ __forceinline__ void stamp_level_start(const LevelCtrl* c) {
   if (c && blockIdx.x == 0 && threadIdx.x == 0) const_cast<LevelCtrl*>(c)->t_start = wall_clock64();
 }
 
-// A new vertex's level: the narrow array when the run uses one (uniform
-// branch), else the 32-bit array.  Narrow overflow (level > kNarrowMaxLevel)
-// stores kNarrowUnreached; the engine reruns such a traversal with wide levels.
-// (narrow: base + level; base + 63 flags a level too deep for the bytes)
-__device__ __forceinline__ void store_level(lvl_t* wide, uint8_t* narrow, int64_t i, lvl_t level, uint8_t base) {
-  if (narrow)
-    narrow[i] = static_cast<uint8_t>(base + (level <= kNarrowMaxLevel ? level : kNarrowMaxLevel + 1));
-  else
-    wide[i] = level;
-}
-
 // Last-arriver hand-offs (scan_units, fused finishes, td_sparse): the last
 // workgroup reads only values the others stored write-through (agent-scope
 // stores / atomics) with agent-scope loads; the agent acquire fence is kept
@@ -94,9 +83,9 @@ __device__ __forceinline__ void scan_finish(const ScanArgs& a, long long carry_c
   a.stats[1] = a.stats[3] = carry_d;
   a.qscan[carry_c] = carry_d;
   *a.ticket = 0u;  // next launch is stream-ordered after this one
-  if (a.ctrl && a.finish) {
-    LevelCtrl c = *a.ctrl;
-    finish_level(a.ctrl, c, carry_c, carry_d, a.seed, a.rec, a.mailbox, a.level);
+  if (a.stamp.ctrl && a.finish) {
+    LevelCtrl c = *a.stamp.ctrl;
+    finish_level(a.stamp, c, carry_c, carry_d);
   }
 }
 

@@ -50,25 +50,24 @@ __device__ __forceinline__ void store_rec(LevelRecDev* rec, const LevelRecDev& r
 // frontier), one thread: level_ctrl_finish on c (the control block as read),
 // the level's record (not for the seed), the control block written back and
 // the mailbox stamped.
-__device__ __forceinline__ void finish_level(LevelCtrl* ctrl, LevelCtrl& c, int64_t cnt, int64_t deg, bool seed,
-                                             LevelRecDev* rec, LevelMailbox* mailbox, int32_t level) {
+__device__ __forceinline__ void finish_level(const LevelStamp s, LevelCtrl& c, int64_t cnt, int64_t deg) {
   LevelRecDev r;
-  level_ctrl_finish(c, cnt, deg, seed, &r);
-  if (!seed && rec) {
+  level_ctrl_finish(c, cnt, deg, s.seed, &r);
+  if (!s.seed && s.rec) {
     r.t0 = c.t_start;
     r.t1 = wall_clock64();
-    store_rec(rec, r);
+    store_rec(s.rec, r);
   }
-  *ctrl = c;
-  if (mailbox) stamp_mailbox(mailbox, c, seed ? -1 : level);
+  *s.ctrl = c;
+  if (s.mailbox) stamp_mailbox(s.mailbox, c, s.seed ? -1 : s.level);
 }
 
 // Several ranks: the level's decision on its all-reduced totals
 // (LevelFinishArgs; stats[2..3] final) -- one thread.
 __device__ __forceinline__ void level_finish_device(const LevelFinishArgs& a) {
-  if (!a.seed && !chain_live(*a.ctrl, a.expect_dir, a.expect_cap)) return;
-  LevelCtrl c = a.seed ? a.ctrl_init : *a.ctrl;
-  finish_level(a.ctrl, c, a.stats[2], a.stats[3], a.seed, a.rec, a.mailbox, a.level);
+  if (!a.stamp.seed && !a.guard.live()) return;
+  LevelCtrl c = a.stamp.seed ? a.ctrl_init : *a.stamp.ctrl;
+  finish_level(a.stamp, c, a.stats[2], a.stats[3]);
 }
 
 // ... for a kernel whose argument block holds `a` (level_finish_block: the
@@ -78,13 +77,13 @@ __device__ __forceinline__ void level_finish_device(const LevelFinishArgs& a) {
 // peer unpack).  (The select stays where `a` is a kernel's own copy: the
 // split form costs td_sparse a spill.)
 __device__ __forceinline__ void level_finish_device_arg(const LevelFinishArgs& a) {
-  if (!a.seed && !chain_live(*a.ctrl, a.expect_dir, a.expect_cap)) return;
-  if (a.seed) {
+  if (!a.stamp.seed && !a.guard.live()) return;
+  if (a.stamp.seed) {
     LevelCtrl c = a.ctrl_init;
-    finish_level(a.ctrl, c, a.stats[2], a.stats[3], true, a.rec, a.mailbox, a.level);
+    finish_level(a.stamp, c, a.stats[2], a.stats[3]);
   } else {
-    LevelCtrl c = *a.ctrl;
-    finish_level(a.ctrl, c, a.stats[2], a.stats[3], false, a.rec, a.mailbox, a.level);
+    LevelCtrl c = *a.stamp.ctrl;
+    finish_level(a.stamp, c, a.stats[2], a.stats[3]);
   }
 }
 

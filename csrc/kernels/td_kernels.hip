@@ -211,17 +211,17 @@ __global__ __launch_bounds__(kThreads) void td_expand_kernel(TdArgs a) {
   __shared__ int s_unvis_on;
   long long q = a.q, m = a.m;
   bool bytes = kOut == TdOut::Bytes, check = a.check_visited;
-  if (a.ctrl) {
-    if (!chain_live(*a.ctrl, 'T', a.max_mf)) return;
-    bytes = a.ctrl->bytes != 0;
-    check = a.ctrl->check_visited != 0;
+  if (!a.guard.live()) return;
+  if (const LevelCtrl* ctrl = a.guard.ctrl) {
+    bytes = ctrl->bytes != 0;
+    check = ctrl->check_visited != 0;
     q = a.dev_stats[0];
     m = a.dev_stats[1];
-    if (a.clear_qv) stamp_level_start(a.ctrl);  // first kernel of the level (no compaction)
-    if (a.clear_qv)
+    if (a.clear_frontier) stamp_level_start(ctrl);  // first kernel of the level (no compaction)
+    if (a.clear_frontier)
       for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < q;
            i += static_cast<int64_t>(gridDim.x) * kThreads) {
-        const vid_t r = a.clear_qv[i];
+        const vid_t r = a.in.qv[i];
         a.clear_frontier[r >> 6] = 0ull;
       }
   }
@@ -251,7 +251,8 @@ __global__ __launch_bounds__(kThreads) void td_expand_kernel(TdArgs a) {
   bool filter = false;
   if constexpr (kHubFilter) {
     filter = a.td_hub_vis && a.g.td_col && m >= a.td_hub_min_edges && blockIdx.x < s_hi - s_lo &&
-             (!a.ctrl || static_cast<double>(a.ctrl->vis_deg) >= a.td_hub_vis_frac * a.ctrl->total_directed);
+             (!a.guard.ctrl ||
+              static_cast<double>(a.guard.ctrl->vis_deg) >= a.td_hub_vis_frac * a.guard.ctrl->total_directed);
     if (filter) {
       const int64_t hw = (a.g.td_nhubs + kWordBits - 1) / kWordBits;
       stage_words<kThreads, kTdMaxHubs / kWordBits>(s_hubvis, a.td_hub_vis, hw);
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void td_expand_kernel(TdArgs a) {
 
   for (long long b = s_lo + blockIdx.x; b < s_hi; b += gridDim.x) {
     const long long e0 = b * kEPB;
-    const int cnt = td_block_owner_map<kThreads, BaseT, kSpan, OwnerT>(a.qscan, a.qbase, a.blk_vstart, b, nblocks, q,
+    const int cnt = td_block_owner_map<kThreads, BaseT, kSpan, OwnerT>(a.in.qscan, a.in.qbase, a.in.blk_vstart, b, nblocks, q,
                                                                        m, s_owner, s_base, s_wmax);
 
     vid_t vk[kItems];
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(kThreads) void td_expand_kernel(TdArgs a) {
         // Plain stores: write-through (sc1) or non-temporal ones measured slower,
         // RMAT-22 88.4 -> 74.8 / 69.3 GTEPS, LJ-sized 56.7 -> 51.4 / 52.0
         // (profiles/r4_s2_td_store_modes.txt).
-        const uint8_t lv = static_cast<uint8_t>(a.narrow_base + a.new_level);
+        const uint8_t lv = a.out.byte();
         bool keep[kItems];
 #pragma unroll
         for (int k = 0; k < kItems; ++k)
@@ -400,7 +401,7 @@ __device__ __forceinline__ void sparse_settle(const TdSparseArgs& a, const vid_t
     if (claimed & (1u << k)) {
       const int64_t r = static_cast<int64_t>(v[k]) - lo;
       DBFS_DCHECK(r >= 0 && r < a.g.rows, 10, v[k]);
-      store_level(a.level, a.level8, r, a.new_level, a.narrow_base);
+      a.out.store(r);
       rs[k] = ro[r];
       re[k] = ro[r + 1];
     }
@@ -455,11 +456,11 @@ __device__ __forceinline__ void sparse_settle(const TdSparseArgs& a, const vid_t
     const long long qs = q0 + ebase[k] + incl[k] - d;
     DBFS_DCHECK(d <= 0 || p < a.g.rows, 4, p);
     if (d > 0) {
-      a.oscan[p] = qs;
-      a.obase[p] = rs[k] - qs;
-      a.oqv[p] = static_cast<vid_t>(static_cast<int64_t>(v[k]) - lo);
+      a.next.qscan[p] = qs;
+      a.next.qbase[p] = rs[k] - qs;
+      a.next.qv[p] = static_cast<vid_t>(static_cast<int64_t>(v[k]) - lo);
     }
-    wave_fill_blocks(a.oblk, d > 0, qs, d, p);
+    wave_fill_blocks(a.next.blk_vstart, d > 0, qs, d, p);
   }
 }
 
@@ -474,7 +475,7 @@ __device__ __forceinline__ void sparse_totals(const TdSparseArgs& a, long long& 
   *a.ticket = 0u;
   a.stats[0] = cnt;
   a.stats[1] = deg;
-  a.oscan[cnt] = deg;
+  a.next.qscan[cnt] = deg;
   a.stats[2] = cnt;
   a.stats[3] = deg;
 }
@@ -583,7 +584,8 @@ __device__ __forceinline__ void sparse_apply(const TdSparseArgs& a, unsigned bx,
   // not (every rank waits for every exchange: the window slots' reuse protocol)
   const bool dx = a.direct.active;
   if (dx && direct_wait(a.direct, s_cnt, nullptr) != kWaitOk) return;
-  if (!live && !chain_live(*a.ctrl, 'T', a.max_mf)) {
+  __builtin_assume(a.guard.ctrl != nullptr);  // (as td_sparse_kernel)
+  if (!live && !a.guard.live()) {
     // a folded level end is a collective: it runs on a no-op chain too
     if (a.end.active && bx == 0) direct_level_end(a.end, a.stats[2], a.stats[3], a.stats, a.fin, s_xend);
     return;
@@ -710,7 +712,11 @@ __global__ __launch_bounds__(kThreads) void td_sparse_kernel(TdSparseArgs a) {
   const long long q = a.dev_stats[0], m = a.dev_stats[1];
   // uniform: the whole grid returns, no workgroup takes a ticket (a direct
   // exchange still publishes, empty)
-  if (!chain_live(*a.ctrl, 'T', a.max_mf)) {
+  // (The sparse kernels run in the device loop only: there is a control
+  // block.  Left to live()'s null test, the several-rank variants reserved 20
+  // bytes of scratch per lane; profiles/kernel_args_regs.txt.)
+  __builtin_assume(a.guard.ctrl != nullptr);
+  if (!a.guard.live()) {
     if (dx && blockIdx.x == 0) {
       direct_publish(a.direct, a.lists, a.list_stride, false);
       // (the fused owner side waits for the peers all the same: a collective)
@@ -718,7 +724,7 @@ __global__ __launch_bounds__(kThreads) void td_sparse_kernel(TdSparseArgs a) {
     }
     return;
   }
-  if (a.first) stamp_level_start(a.ctrl);
+  if (a.first) stamp_level_start(a.guard.ctrl);
   const long long nblocks = (m + kTdEdgesPerBlock - 1) / kTdEdgesPerBlock;
   // Only the workgroups that have an edge block take part (at least one, for
   // the finish): the others return before the ticket -- on a level of a few
@@ -730,17 +736,13 @@ __global__ __launch_bounds__(kThreads) void td_sparse_kernel(TdSparseArgs a) {
   // workgroups' per-wave atomics on the one counter queue (~90 per us); a
   // small level keeps the per-wave form (the workgroup form's barriers cost
   // it ~2 us).  (Workgroup-uniform: nblocks is.)
-#ifdef DBFS_NO_WG_SETTLE
-  constexpr bool wg_settle = false;  // (diagnostic build: same-box A/B)
-#else
   const bool wg_settle = nblocks >= kTdWgSettleBlocks;
-#endif
   const int t = threadIdx.x;
   const int64_t gtid = static_cast<int64_t>(blockIdx.x) * kThreads + t;
   const int64_t gstride = static_cast<int64_t>(active) * kThreads;
   // the input vertices' frontier bits (the bitmap is not read here)
   for (int64_t i = gtid; i < q; i += gstride) {
-    const vid_t r = a.qv[i];
+    const vid_t r = a.in.qv[i];
     a.frontier_in[r >> 6] = 0ull;
   }
 
@@ -748,7 +750,7 @@ __global__ __launch_bounds__(kThreads) void td_sparse_kernel(TdSparseArgs a) {
   const uint64_t lo = static_cast<uint64_t>(a.g.lo), rows = static_cast<uint64_t>(a.g.rows);
   for (long long b = blockIdx.x; b < nblocks; b += active) {
     const long long e0 = b * kTdEdgesPerBlock;
-    const int cnt = td_block_owner_map<kThreads>(a.qscan, a.qbase, a.blk_vstart, b, nblocks, q, m, s_owner, s_base,
+    const int cnt = td_block_owner_map<kThreads>(a.in.qscan, a.in.qbase, a.in.blk_vstart, b, nblocks, q, m, s_owner, s_base,
                                                  s_wmax);
     // (A) all items' claims in flight together: col, visited, fetch-or
     vid_t v[kItems];
@@ -836,8 +838,8 @@ __global__ __launch_bounds__(kThreads) void td_sparse_kernel(TdSparseArgs a) {
   if (t != 0) return;
   long long cnt = 0, deg = 0;
   sparse_totals(a, cnt, deg);
-  LevelCtrl c = *a.ctrl;
-  finish_level(a.ctrl, c, cnt, deg, false, a.rec, a.mailbox, a.level_index);
+  LevelCtrl c = *a.stamp.ctrl;
+  finish_level(a.stamp, c, cnt, deg);
 }
 
 // Sparse top-down level read straight from the bitmap a bottom-up level left
@@ -858,14 +860,17 @@ __global__ __launch_bounds__(kBlock) void td_sparse_bits_kernel(TdSparseArgs a) 
   __shared__ eid_t s_rs[kBlock];        // ... and row starts
   __shared__ int s_last;
   const bool dx = kLists && a.lists && a.direct.active;
-  if (!chain_live(*a.ctrl, 'T', a.max_mf)) {
+  __builtin_assume(a.guard.ctrl != nullptr);  // (as td_sparse_kernel)
+  if (!a.guard.live()) {
     if (dx && blockIdx.x == 0) {
       direct_publish(a.direct, a.lists, a.list_stride, false);
       if (a.fuse_apply) sparse_apply<kBlock, false>(a, 0, 1);  // (a collective: as td_sparse)
     }
     return;
   }
-  stamp_level_start(a.ctrl);
+  // (through the pointer the finish writes: with guard.ctrl here the one-rank
+  // variant reserved 36 bytes of scratch per lane)
+  stamp_level_start(a.stamp.ctrl);
   const int t = threadIdx.x;
   const int lane = lane_id();
   const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(t >> 6));  // (wave-uniform)
@@ -980,8 +985,8 @@ __global__ __launch_bounds__(kBlock) void td_sparse_bits_kernel(TdSparseArgs a) 
   if (t != 0) return;
   long long cnt = 0, deg = 0;
   sparse_totals(a, cnt, deg);
-  LevelCtrl c = *a.ctrl;
-  finish_level(a.ctrl, c, cnt, deg, false, a.rec, a.mailbox, a.level_index);
+  LevelCtrl c = *a.stamp.ctrl;
+  finish_level(a.stamp, c, cnt, deg);
 }
 
 
@@ -1025,14 +1030,14 @@ __global__ __launch_bounds__(kTdThreads) void bin_pass_kernel(BinArgs a) {
   __shared__ int32_t s_wmax[kTdThreads / kWave];
   __shared__ unsigned s_cnt[kBinMaxBins];
   __shared__ long long s_start[kFill ? kBinMaxBins : 1];
-  if (!chain_live(*a.ctrl, 'T', 0)) return;
+  if (!a.guard.live()) return;
   const long long q = a.dev_stats[0], m = a.dev_stats[1];
   const int t = threadIdx.x;
-  if (!kFill && a.clear_qv) {
-    stamp_level_start(a.ctrl);  // first kernel of the level (no compaction ran)
+  if (!kFill && a.clear_frontier) {
+    stamp_level_start(a.guard.ctrl);  // first kernel of the level (no compaction ran)
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kTdThreads + t; i < q;
          i += static_cast<int64_t>(gridDim.x) * kTdThreads)
-      a.clear_frontier[a.clear_qv[i] >> 6] = 0ull;
+      a.clear_frontier[a.in.qv[i] >> 6] = 0ull;
   }
   for (int k = t; k < a.nbins; k += kTdThreads) s_cnt[k] = 0;
   if constexpr (kFill) {
@@ -1064,7 +1069,7 @@ __global__ __launch_bounds__(kTdThreads) void bin_pass_kernel(BinArgs a) {
   const vid_t* __restrict__ col = a.g.col;
   for (long long b = blockIdx.x; b < nblocks; b += gridDim.x) {
     const long long e0 = b * kTdEdgesPerBlock;
-    const int cnt = td_block_owner_map<kTdThreads>(a.qscan, a.qbase, a.blk_vstart, b, nblocks, q, m, s_owner,
+    const int cnt = td_block_owner_map<kTdThreads>(a.in.qscan, a.in.qbase, a.in.blk_vstart, b, nblocks, q, m, s_owner,
                                                    s_base, s_wmax);
     vid_t v[kItems];
 #pragma unroll
@@ -1093,7 +1098,7 @@ __global__ __launch_bounds__(kTdThreads) void bin_pass_kernel(BinArgs a) {
 // bin's total.
 __global__ __launch_bounds__(kTdThreads) void bin_scan_kernel(BinArgs a) {
   __shared__ long long s_part[kTdThreads / kWave];
-  if (!chain_live(*a.ctrl, 'T', 0)) return;
+  if (!a.guard.live()) return;
   uint32_t* row = a.cnt + static_cast<int64_t>(blockIdx.x) * a.grid;
   const int t = threadIdx.x;
   const int per = (a.grid + kTdThreads - 1) / kTdThreads;
@@ -1131,7 +1136,7 @@ __global__ __launch_bounds__(kBinThreads) void bin_apply_kernel(BinArgs a) {
   __shared__ word_t s_vis[kMaxWords];
   __shared__ word_t s_new[kMaxWords];
   __shared__ long long s_part[kBinThreads / kWave];
-  if (!chain_live(*a.ctrl, 'T', 0)) return;
+  if (!a.guard.live()) return;
   const int t = threadIdx.x;
   const int lane = lane_id();
   const int64_t bin = blockIdx.x;
@@ -1197,9 +1202,9 @@ __global__ __launch_bounds__(kBinThreads) void bin_apply_kernel(BinArgs a) {
 
 // out bit h = visited bit of td_hub_vertex[h]: one wave per hub word.
 __global__ __launch_bounds__(kBlock) void hub_visited_kernel(HubVisitedArgs a) {
-  if (a.ctrl && (!chain_live(*a.ctrl, 'T', 0) || a.ctrl->m_f < a.min_edges ||
-                 static_cast<double>(a.ctrl->vis_deg) < a.vis_frac * a.ctrl->total_directed))
-    return;
+  if (!a.guard.live()) return;
+  if (const LevelCtrl* ctrl = a.guard.ctrl)
+    if (ctrl->m_f < a.min_edges || static_cast<double>(ctrl->vis_deg) < a.vis_frac * ctrl->total_directed) return;
   const int64_t w = static_cast<int64_t>(blockIdx.x) * (kBlock / kWave) + (threadIdx.x >> 6);
   const int64_t h = w * kWave + lane_id();
   const bool bit = h < a.g.td_nhubs && test_bit(a.visited, a.g.td_hub_vertex[h]);
@@ -1213,7 +1218,7 @@ __global__ __launch_bounds__(kBlock) void hub_visited_kernel(HubVisitedArgs a) {
 // filter word written, nothing to clear between levels.
 constexpr int kUnvisChunk = 64;
 __global__ __launch_bounds__(kBlock) void unvis_filter_kernel(UnvisArgs a) {
-  if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
+  if (!a.guard.live()) return;
   __shared__ word_t s_f[kUnvisChunk];
   const int t = threadIdx.x;
   const int64_t w0 = static_cast<int64_t>(blockIdx.x) * kUnvisChunk;
@@ -1260,8 +1265,8 @@ __global__ __launch_bounds__(kBlock) void unvis_filter_kernel(UnvisArgs a) {
 // HubApplyArgs: 16 marks per thread (kTdMaxHubs is a multiple of 16; the
 // marks past td_nhubs stay zero).
 __global__ __launch_bounds__(kBlock) void hub_apply_kernel(HubApplyArgs a) {
-  if (a.ctrl && !chain_live(*a.ctrl, 'T', a.max_mf)) return;
-  const uint8_t lv = static_cast<uint8_t>(a.narrow_base + a.new_level);
+  if (!a.guard.live()) return;
+  const uint8_t lv = a.out.byte();
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock * 16;
   for (int64_t i = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * 16; i < a.g.td_nhubs; i += stride) {
     uint4* p = reinterpret_cast<uint4*>(a.mark + i);
@@ -1273,7 +1278,7 @@ __global__ __launch_bounds__(kBlock) void hub_apply_kernel(HubApplyArgs a) {
       if ((w[j >> 2] >> (8 * (j & 3))) & 0xFFu) {
         DBFS_DCHECK(i + j < a.g.td_nhubs, 9, i + j);
         const vid_t v = a.g.td_hub_vertex[i + j];
-        a.level8[v] = lv;
+        a.out.level8[v] = lv;
       }
     *p = make_uint4(0u, 0u, 0u, 0u);
   }
@@ -1318,14 +1323,16 @@ void td_expand(const TdArgs& a, hipStream_t st) {
     ~Report() { td_stats_report(st); }
   } report{st};
 #endif
-  if (a.ctrl) {
-    // device loop: fixed grid, size and output mode read on the device
+  if (a.guard.ctrl) {
+    // device loop (dense chains: bits or bytes, never owner lists): fixed
+    // grid, size and output mode read on the device
+    DBFS_CHECK(!a.lists, "td_expand: owner lists belong to the host loop");
     if (a.grid <= 0) return;
     const bool b32 = a.g.nnz <= (int64_t(1) << 32);
     const int64_t fgrid = a.grid_filter > 0 ? a.grid_filter : a.grid;
 #define LAUNCH_TD_DEV(OUT, F, B) \
   td_expand_kernel<OUT, kTdThreads, F, B><<<td_resident_grid<OUT, F, B>(F ? fgrid : a.grid), kTdThreads, 0, st>>>(a)
-    if (a.unvis && !a.lists) {
+    if (a.unvis) {
       // the filter variant, then the plain one: the level runs in one of
       // them (the filter's density, read by both)
       DBFS_CHECK(a.unvis_pop, "td_expand: an unvisited filter without its chunk counts");
@@ -1336,9 +1343,7 @@ void td_expand(const TdArgs& a, hipStream_t st) {
         td_expand_kernel<TdOut::Dyn, 1024, false, false, true>
             <<<td_resident_grid<TdOut::Dyn, false, false, 1024, true>(a.grid), 1024, 0, st>>>(a);
     }
-    if (a.lists)
-      LAUNCH_TD_DEV(TdOut::Lists, false, false);
-    else if (a.td_hub_vis && b32)
+    if (a.td_hub_vis && b32)
       LAUNCH_TD_DEV(TdOut::Dyn, true, true);
     else if (a.td_hub_vis)
       LAUNCH_TD_DEV(TdOut::Dyn, true, false);

@@ -34,8 +34,10 @@ class BFSResult:
     @property
     def chains(self) -> List[Any]:
         """Device loop: every level chain enqueued, in order, as an 8-tuple
-        (level, form, list capacity, gathered, pushed, unvisited filter, parts,
-        hub cut) -- form T / S / L / B / X (mispredicted chains included);
+        (level, form, cap, gathered, pushed, unvisited filter, parts, hub cut)
+        -- form T (dense top-down) / S (sparse top-down) / X (binned top-down)
+        / B (bottom-up), mispredicted chains included; cap (index 2): the
+        frontier edges a sparse chain stays live for (0: any);
         parts > 1 (index 6): a split top-down level (Options td_split_edges /
         td_split_parts); hub cut (index 7): a first bottom-up level enqueued
         with the hub cut (Options bu_cut_edges)."""
