@@ -245,13 +245,16 @@ class CpuBackend final : public Backend {
   void ms_pull(const MsPullArgs& a) override {
     const MsState& s = a.s;
     const ShardView& g = s.g;
+    // (a directed graph: the in-edge rows; ms_record sums out-degrees from s.g)
+    const eid_t* row_off = s.directed ? s.in_row_off : g.row_off;
+    const vid_t* col = s.directed ? s.in_col : g.col;
     std::fill(s.stats, s.stats + kMsStats, int64_t(0));
     for (int64_t v = 0; v < g.rows; ++v) {
       const word_t need = ~s.seen[v] & s.batch_mask;
       word_t got = 0;
       if (need)
-        for (eid_t e = g.row_off[v]; e < g.row_off[v + 1]; ++e) {
-          got |= s.front[g.col[e]];
+        for (eid_t e = row_off[v]; e < row_off[v + 1]; ++e) {
+          got |= s.front[col[e]];
           if ((got & need) == need) break;
         }
       const word_t nw = got & need;
@@ -317,9 +320,16 @@ class CpuBackend final : public Backend {
         for (eid_t e = g.row_off[r]; e < g.row_off[r + 1]; ++e) {
           const vid_t w = g.col[e];
           const int lw = level(w, s);
-          if (lu == none && lw == none) continue;
-          if ((lu == none) != (lw == none)) { ++cross; continue; }
-          if (lu - lw > 1 || lw - lu > 1) ++gap;
+          if (a.directed) {
+            // (in-edge row of u: the entry is w -> u)
+            if (lw == none) continue;
+            if (lu == none) { ++cross; continue; }
+            if (lu - lw > 1) ++gap;
+          } else {
+            if (lu == none && lw == none) continue;
+            if ((lu == none) != (lw == none)) { ++cross; continue; }
+            if (lu - lw > 1 || lw - lu > 1) ++gap;
+          }
           if (lw == lu - 1 && !has_parent) {
             has_parent = true;
             par = w;
@@ -724,9 +734,16 @@ class CpuBackend final : public Backend {
       bool has_parent = false;
       for (eid_t e = a.g.row_off[r]; e < a.g.row_off[r + 1]; ++e) {
         const lvl_t lv = a.level_global[a.g.col[e]];
-        if (lu == kUnreached && lv == kUnreached) continue;
-        if ((lu == kUnreached) != (lv == kUnreached)) { ++cross; continue; }
-        if (lu - lv > 1 || lv - lu > 1) ++gap;
+        if (a.directed) {
+          // (in-edge row of u: the entry is col[e] -> u)
+          if (lv == kUnreached) continue;
+          if (lu == kUnreached) { ++cross; continue; }
+          if (lu - lv > 1) ++gap;
+        } else {
+          if (lu == kUnreached && lv == kUnreached) continue;
+          if ((lu == kUnreached) != (lv == kUnreached)) { ++cross; continue; }
+          if (lu - lv > 1 || lv - lu > 1) ++gap;
+        }
         if (lv == lu - 1) has_parent = true;
       }
       if (lu != kUnreached && u != a.src && !has_parent) ++orphan;
@@ -771,8 +788,9 @@ class CpuBackend final : public Backend {
     }
   }
 
-  void sort_rows_by_id(const eid_t* ro, vid_t* col, int64_t rows, int64_t n) override {
+  void sort_rows_by_id(const eid_t* ro, vid_t* col, int64_t rows, int64_t n, bool exact_long) override {
     (void)n;
+    (void)exact_long;  // (every row is sorted exactly here)
     for (int64_t r = 0; r < rows; ++r) std::sort(col + ro[r], col + ro[r + 1]);
   }
 
@@ -973,6 +991,16 @@ class CpuBackend final : public Backend {
       out[cursor[u[i] / part]++] = (static_cast<uint64_t>(u[i]) << 32) | v[i];
       out[cursor[v[i] / part]++] = (static_cast<uint64_t>(v[i]) << 32) | u[i];
     }
+    (void)nranks;
+  }
+  void in_route_count(const ShardView& g, int64_t part, int nranks, int64_t* counts) override {
+    for (eid_t e = 0; e < g.nnz; ++e) ++counts[g.col[e] / part];
+    (void)nranks;
+  }
+  void in_route_fill(const ShardView& g, int64_t part, int nranks, int64_t* cursor, uint64_t* out) override {
+    for (int64_t r = 0; r < g.rows; ++r)
+      for (eid_t e = g.row_off[r]; e < g.row_off[r + 1]; ++e)
+        out[cursor[g.col[e] / part]++] = (static_cast<uint64_t>(g.col[e]) << 32) | static_cast<uint64_t>(g.lo + r);
     (void)nranks;
   }
   void entries_count(const uint64_t* e, int64_t k, int64_t lo, eid_t* deg) override {

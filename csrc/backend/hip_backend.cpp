@@ -373,7 +373,7 @@ class HipBackend final : public Backend {
     release_(count);
   }
 
-  void sort_rows_by_id(const eid_t* ro, vid_t* col, int64_t rows, int64_t n) override {
+  void sort_rows_by_id(const eid_t* ro, vid_t* col, int64_t rows, int64_t n, bool exact_long) override {
     on();
     eid_t nnz = 0;
     HIP_CHECK(hipMemcpyAsync(&nnz, ro + rows, sizeof(nnz), hipMemcpyDeviceToHost, st_));
@@ -384,7 +384,7 @@ class HipBackend final : public Backend {
     HIP_CHECK(hipMalloc(&list, static_cast<size_t>(std::max<int64_t>(rows, 1)) * sizeof(int64_t)));
     HIP_CHECK(hipMalloc(&count, sizeof(unsigned long long)));
     HIP_CHECK(hipMalloc(&tmp, static_cast<size_t>(std::max<eid_t>(nnz, 1)) * sizeof(vid_t)));
-    kern::sort_rows_by_id(ro, col, rows, n, list, count, tmp, st_);
+    kern::sort_rows_by_id(ro, col, rows, n, list, count, tmp, exact_long, st_);
     chk();
     HIP_CHECK(hipStreamSynchronize(st_));
     release_(list);
@@ -420,6 +420,18 @@ class HipBackend final : public Backend {
     DBFS_CHECK(nranks <= kern::route_max_ranks(), "edge routing supports at most 1024 ranks");
     kern::route_edges_fill(u, v, m, part, nranks, cursor, out, st_);
     HIP_CHECK(hipGetLastError());
+  }
+  void in_route_count(const ShardView& g, int64_t part, int nranks, int64_t* counts) override {
+    DBFS_CHECK(nranks <= kern::route_max_ranks(), "edge routing supports at most 1024 ranks");
+    on();
+    kern::in_route_count(g, part, nranks, counts, st_);
+    chk();
+  }
+  void in_route_fill(const ShardView& g, int64_t part, int nranks, int64_t* cursor, uint64_t* out) override {
+    DBFS_CHECK(nranks <= kern::route_max_ranks(), "edge routing supports at most 1024 ranks");
+    on();
+    kern::in_route_fill(g, part, nranks, cursor, out, st_);
+    chk();
   }
   void entries_count(const uint64_t* e, int64_t k, int64_t lo, eid_t* deg) override {
     kern::entries_count(e, k, lo, deg, st_);

@@ -69,6 +69,7 @@ struct Args {
   bool phase_timing = false;
   bool hub_sort = true;
   bool directed = false;
+  bool mode_given = false;            // --mode on the command line (--directed turns only the default into td)
 };
 
 [[noreturn]] void usage(const char* msg = nullptr) {
@@ -84,7 +85,8 @@ struct Args {
                "       --batch --validate (every pass's levels checked on the device, all its sources at once)\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
-               "                   top-down modes only)\n"
+               "                   top-down modes only; --batch and --validate work on the in-edge shard,\n"
+               "                   built on the device on first use)\n"
                "       --level-csv FILE (per-level records of every run: root,level,dir,frontier,...,ms)\n");
   std::exit(2);
 }
@@ -102,7 +104,10 @@ Args parse(int argc, char** argv) {
     else if (s == "--virtual-ranks") a.virtual_ranks = std::stoi(next());
     else if (s == "--device") a.device = std::stoi(next());
     else if (s == "--cpu") a.cpu = true;
-    else if (s == "--mode") a.mode = next();
+    else if (s == "--mode") {
+      a.mode = next();
+      a.mode_given = true;
+    }
     else if (s == "--alpha") a.alpha = std::stod(next());
     else if (s == "--beta") a.beta = std::stod(next());
     else if (s == "--bu-lane-limit") a.bu_lane_limit = std::stoi(next());
@@ -151,12 +156,13 @@ Args parse(int argc, char** argv) {
   }
   if (a.gpus < 1) usage("--gpus must be >= 1");
   if (a.directed) {
-    // bottom-up searches in-edges, which a directed CSR does not hold; the
-    // Graph500 checks assume an undirected graph
+    // a single-source traversal is top-down only (the bottom-up kernels take
+    // their degrees from their own rows); --batch pulls over the in-edge shard
+    // and --validate checks the directed level rules on it
     if (synth) usage("--directed applies to edge-list input only");
-    if (a.mode == "bu") usage("--directed needs a top-down mode (td, ref, simple, scan)");
+    if (a.mode == "bu" || (a.mode == "do" && a.mode_given))
+      usage("--directed needs a top-down mode (td, ref, simple, scan)");
     if (a.mode == "do") a.mode = "td";
-    if (a.validate) usage("--validate checks undirected graphs only (the oracle comparison stays on)");
   }
   return a;
 }

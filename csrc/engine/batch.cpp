@@ -91,6 +91,14 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
 
   MsState s;
   s.g = g_.view();
+  s.in_row_off = s.g.row_off;
+  s.in_col = s.g.col;
+  if (opt_.directed) {  // (built by run_batch, before the timed window)
+    const ShardView in = g_.in_view();
+    s.in_row_off = in.row_off;
+    s.in_col = in.col;
+    s.directed = true;
+  }
   s.seen = b.seen.data();
   s.front = b.front.data();
   s.next = b.next.data();
@@ -180,6 +188,7 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
     s.level = level;
     s.active_out = b.list[cur ^ 1].data();
     s.seq = ++b.seq;
+    inject_batch_fault(level);
     if (pull) {
       MsPullArgs pa;
       pa.s = s;
@@ -240,7 +249,7 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
     out.reached[first + t] = reached;
     out.dist_sum[first + t] = dist;
     out.depth[first + t] = static_cast<int>(d.size());
-    out.edges[first + t] = deg[t] / 2;
+    out.edges[first + t] = opt_.directed ? deg[t] : deg[t] / 2;
   }
   return 0;
 }
@@ -249,11 +258,11 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirectio
                               bool keep_parents) {
   DBFS_CHECK(keep_levels || !(validate || keep_parents),
              "run_batch: validate and keep_parents read the level matrix (keep_levels)");
-  DBFS_CHECK(!opt_.directed, "run_batch: directed graphs are not supported (the pull form searches in-edges)");
   DBFS_CHECK(!sources.empty(), "run_batch: no sources");
   for (int64_t v : sources) DBFS_CHECK(v >= 0 && v < part_.n, "run_batch: source vertex out of range");
   DBFS_CHECK(part_.nranks == 1 || dir != BatchDirection::Push,
              "run_batch: the push form runs on one rank only (several ranks: every level is a pull)");
+  build_in_edges();  // (a directed graph's first batch; outside the timed window)
   const int64_t k = static_cast<int64_t>(sources.size());
   BatchResult out;
   out.sources = sources;
@@ -296,6 +305,7 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirectio
     be_.synchronize();
     const auto t1 = std::chrono::steady_clock::now();
     ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    check_device();  // (checked build: a violation a kernel of the pass recorded fails the batch)
     if (keep_levels) {
       batch_pending_first_ = first;
       batch_pending_k_ = kp;
@@ -354,7 +364,9 @@ void Engine::collect_batch_levels(int64_t first, int k) {
 
 // Backend::ms_check on the pass's matrix (several ranks: the all-gathered
 // slices, W vertices each, so global vertex v is row v -- the simple form, as
-// the rest of the several-rank batch).
+// the rest of the several-rank batch).  A directed graph is checked by the
+// directed rules in one walk over its in-edge shard, where every stored entry
+// u -> v appears once, in v's row.
 void Engine::check_batch_pass(const int64_t* src, int k, int64_t* viol, bool parents, int64_t first) {
   const int P = part_.nranks;
   const int64_t W = part_.part;
@@ -367,7 +379,8 @@ void Engine::check_batch_pass(const int64_t* src, int k, int64_t* viol, bool par
     comm_.allgather(b.lvl.data(), all.data(), bytes);
   }
   MsCheckArgs ca;
-  ca.g = g_.view();
+  ca.g = check_view();
+  ca.directed = opt_.directed;
   ca.lvl = P > 1 ? all.data() : b.lvl.data();
   ca.lvl_bytes = b.lvl_bytes;
   ca.lvl_rows = W * P;
@@ -410,6 +423,7 @@ void Engine::check_batch_pass(const int64_t* src, int k, int64_t* viol, bool par
     }
   }
   be_.synchronize();  // (a rank that copied nothing back: check_ms still ends with the work done)
+  check_device();
 }
 
 std::vector<int64_t> Engine::validate_batch_pass(const std::vector<int64_t>& sources) {

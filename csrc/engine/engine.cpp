@@ -131,6 +131,8 @@ std::vector<std::pair<std::string, double>> engine_option_map(const EngineOption
 
 // ---- DeviceGraph ----------------------------------------------------------------
 
+static void throw_device_check(Backend& be, int rank);  // (below, with Engine::check_device)
+
 std::unique_ptr<DeviceGraph> DeviceGraph::from_host(Backend& be, const HostCSR& csr, const Partition& part,
                                                     int rank) {
   DBFS_CHECK(csr.n == part.n, "partition vertex count does not match the graph");
@@ -281,6 +283,93 @@ std::unique_ptr<DeviceGraph> DeviceGraph::from_file(Backend& be, Comm& comm, con
   auto g = from_edges(be, comm, part, rank, es.m, es.u.data(), es.v.data(), es.local_edges());
   g->ingest_ = {es.byte_begin, es.byte_end, es.local_edges()};
   return g;
+}
+
+void DeviceGraph::build_in_edges(Comm& comm) {
+  if (has_in_edges_) return;
+  DBFS_CHECK(comm.size() == part_.nranks && comm.rank() == rank_, "communicator does not match the shard");
+  Backend& be = *be_;
+  comm.bind_backend(be_);
+  const int P = part_.nranks;
+  // (1) the owned out-entries per owner of their target, (2) the counts to the owners
+  std::vector<int64_t> sc(static_cast<size_t>(P), 0), rc(static_cast<size_t>(P), 0);
+  std::vector<int64_t> sd(static_cast<size_t>(P), 0), rd(static_cast<size_t>(P), 0);
+  DBuf<uint64_t> send;
+  {
+    DBuf<int64_t> cnt(be, static_cast<size_t>(P)), rcnt(be, static_cast<size_t>(P));
+    be.memset_async(cnt.data(), 0, cnt.bytes());
+    be.in_route_count(view(), part_.part, P, cnt.data());
+    comm.alltoall(cnt.data(), rcnt.data(), sizeof(int64_t));
+    be.to_host(sc.data(), cnt.data(), cnt.bytes());
+    be.to_host(rc.data(), rcnt.data(), rcnt.bytes());
+    for (int r = 1; r < P; ++r) {
+      sd[r] = sd[r - 1] + sc[r - 1];
+      rd[r] = rd[r - 1] + rc[r - 1];
+    }
+    DBFS_CHECK(sd[P - 1] + sc[P - 1] == nnz_, "in-edge routing lost entries");
+    // (3) the entries (target << 32 | source), grouped by owner
+    send = DBuf<uint64_t>(be, static_cast<size_t>(std::max<int64_t>(nnz_, 1)));
+    be.to_device(cnt.data(), sd.data(), sd.size() * sizeof(int64_t));  // cursors = segment starts
+    be.in_route_fill(view(), part_.part, P, cnt.data(), send.data());
+    be.synchronize();
+  }
+  // (4) to their owners
+  const int64_t nrecv = rd[P - 1] + rc[P - 1];
+  DBuf<uint64_t> recv(be, static_cast<size_t>(std::max<int64_t>(nrecv, 1)));
+  comm.alltoallv(send.data(), sc.data(), sd.data(), recv.data(), rc.data(), rd.data(), sizeof(uint64_t));
+  be.synchronize();
+  send.reset();
+  // (5) the rows: degrees -> offsets -> fill
+  in_row_off_ = DBuf<eid_t>(be, static_cast<size_t>(rows_ + 1));
+  be.memset_async(in_row_off_.data(), 0, in_row_off_.bytes());
+  be.entries_count(recv.data(), nrecv, lo_, in_row_off_.data());
+  be.exclusive_scan(in_row_off_.data(), rows_);
+  eid_t nnz = 0;
+  be.to_host(&nnz, in_row_off_.data() + rows_, sizeof(eid_t));
+  DBFS_CHECK(nnz == nrecv, "in-edge entries outside this rank's rows");
+  in_nnz_ = nnz;
+  in_col_ = DBuf<vid_t>(be, static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+  {
+    DBuf<eid_t> cursor(be, static_cast<size_t>(std::max<int64_t>(rows_, 1)));
+    be.copy_async(cursor.data(), in_row_off_.data(), static_cast<size_t>(rows_) * sizeof(eid_t));
+    be.entries_fill(recv.data(), nrecv, lo_, cursor.data(), in_col_.data());
+    be.synchronize();
+  }
+  recv.reset();
+  // (6) every row ascending, the long ones too
+  be.sort_rows_by_id(in_row_off_.data(), in_col_.data(), rows_, part_.n, true);
+  be.synchronize();
+  has_in_edges_ = true;
+  // checked build: a bounds violation of the build's kernels fails it here
+  const FaultSpec fault = FaultSpec::from_env();
+  if (fault.kind == "in_edges_device" && fault.rank == rank_) be.inject_device_check();
+  throw_device_check(be, rank_);
+}
+
+ShardView DeviceGraph::in_view() const {
+  DBFS_CHECK(has_in_edges_, "in_view: the in-edge shard has not been built (build_in_edges)");
+  ShardView v;
+  v.row_off = in_row_off_.data();
+  v.col = in_col_.data();
+  v.n = part_.n;
+  v.lo = lo_;
+  v.rows = rows_;
+  v.nnz = in_nnz_;
+  return v;
+}
+
+HostCSR DeviceGraph::in_edges_to_host() const {
+  DBFS_CHECK(has_in_edges_, "in_edges_to_host: the in-edge shard has not been built (build_in_edges)");
+  HostCSR h;
+  h.n = part_.n;
+  h.row_lo = lo_;
+  h.rows = rows_;
+  h.input_edges = input_edges_;
+  h.row_off.resize(static_cast<size_t>(rows_ + 1));
+  h.col.resize(static_cast<size_t>(in_nnz_));
+  be_->to_host(h.row_off.data(), in_row_off_.data(), h.row_off.size() * sizeof(eid_t));
+  if (in_nnz_) be_->to_host(h.col.data(), in_col_.data(), h.col.size() * sizeof(vid_t));
+  return h;
 }
 
 ShardView DeviceGraph::view() const {
@@ -556,7 +645,9 @@ void Engine::read_level_stats(int64_t* host_stats) {
 // at the start of level L of every run: `throw` raises an Error (in-process
 // ranks abort their group), `exit` ends the process with status 17 (a crashed
 // rank), `hang` stops participating (peers must time out), `device` records
-// a device-check violation (the run fails when it ends), `delay` enqueues the
+// a device-check violation (the run fails when it ends), `batch_device` the
+// same at level L of a batch pass (run_batch fails after the pass),
+// `in_edges_device` during DeviceGraph::build_in_edges, `delay` enqueues the
 // level ms late; kind=late_wg[,us=U] (every rank, every level) makes the
 // workgroups of a sparse top-down level that take no ticket start U us late
 // on the device (TdSparseArgs::late_ticks).  Used by the failure-detection
@@ -583,8 +674,10 @@ FaultSpec FaultSpec::from_env() {
     pos = comma + 1;
   }
   DBFS_CHECK(f.kind == "throw" || f.kind == "exit" || f.kind == "hang" || f.kind == "device" || f.kind == "delay" ||
-                 f.kind == "rccl_init" || f.kind == "peer_init" || f.kind == "late_wg",
-             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|delay|rccl_init|peer_init|late_wg");
+                 f.kind == "rccl_init" || f.kind == "peer_init" || f.kind == "late_wg" || f.kind == "batch_device" ||
+                 f.kind == "in_edges_device",
+             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|in_edges_device|delay|rccl_init|"
+             "peer_init|late_wg");
   // (rccl_init / peer_init: the communicators' setup fails -- NcclComm /
   // PeerComm read them; late_wg: every sparse top-down level's ticket-less
   // workgroups start late, on every rank (DeviceLoop::emit_sparse) -- the
@@ -593,18 +686,28 @@ FaultSpec FaultSpec::from_env() {
   return f;
 }
 
-// Device-checked build: the first bounds violation a kernel recorded during
-// the traversal fails the run (codes: DBFS_DCHECK sites in the {bfs,td,bu}_kernels.hip files).
-void Engine::check_device() {
-  const uint64_t v = be_.take_device_check();
+// Device-checked build: the first bounds violation a kernel recorded since
+// the last read fails the call that reads it (codes: the DBFS_DCHECK sites of
+// the kernel files).  Read after every traversal, every batch pass and its
+// check, every single-source validation / parent tree and the in-edge build;
+// without the checked build there is no word to read and nothing is waited for.
+static void throw_device_check(Backend& be, int rank) {
+  const uint64_t v = be.take_device_check();
   if (v == 0) return;
   char buf[160];
-  std::snprintf(buf, sizeof(buf), "device check failed on rank %d: code %llu, detail %llu", comm_.rank(),
+  std::snprintf(buf, sizeof(buf), "device check failed on rank %d: code %llu, detail %llu", rank,
                 static_cast<unsigned long long>(v >> 48), static_cast<unsigned long long>(v & 0xFFFFFFFFFFFFull));
   throw Error(buf);
 }
 
+void Engine::check_device() { throw_device_check(be_, comm_.rank()); }
+
+void Engine::inject_batch_fault(int level) {
+  if (fault_.kind == "batch_device" && fault_.rank == comm_.rank() && fault_.level == level) be_.inject_device_check();
+}
+
 void Engine::inject_fault(int level) {
+  if (fault_.kind == "batch_device" || fault_.kind == "in_edges_device") return;  // (not a traversal's)
   if (fault_.rank != comm_.rank() || fault_.level != level) return;
   if (fault_.kind == "device") {
     // a kernel-side bounds violation (recorded, not raised: the traversal
@@ -1287,12 +1390,22 @@ void Engine::gather_levels_device(DBuf<lvl_t>& full) {
   comm_.allgather(send.data(), full.data(), static_cast<size_t>(part) * sizeof(lvl_t));
 }
 
+void Engine::build_in_edges() {
+  if (opt_.directed) g_.build_in_edges(comm_);
+}
+
+ShardView Engine::check_view() {
+  if (!opt_.directed) return g_.view();
+  g_.build_in_edges(comm_);
+  return g_.in_view();
+}
+
 std::vector<int64_t> Engine::parents_local(int64_t source) {
   DBuf<lvl_t> full;
   gather_levels_device(full);
   DBuf<int64_t> par(be_, static_cast<size_t>(std::max<int64_t>(g_.rows(), 1)));
   ParentArgs pa;
-  pa.g = g_.view();
+  pa.g = check_view();  // (a directed graph: the same rule on the in-edge rows)
   pa.level_global = full.data();
   pa.src = source;
   pa.parent = par.data();
@@ -1300,6 +1413,7 @@ std::vector<int64_t> Engine::parents_local(int64_t source) {
   std::vector<int64_t> h(static_cast<size_t>(g_.rows()));
   if (!h.empty()) be_.to_host(h.data(), par.data(), h.size() * sizeof(int64_t));
   else be_.synchronize();
+  check_device();
   return h;
 }
 
@@ -1323,7 +1437,8 @@ std::vector<int64_t> Engine::validate(int64_t source) {
   DBuf<int64_t> out(be_, 3);
   be_.memset_async(out.data(), 0, out.bytes());
   ValidateArgs va;
-  va.g = g_.view();
+  va.g = check_view();
+  va.directed = opt_.directed;
   va.level_global = full.data();
   va.src = source;
   va.out = out.data();
@@ -1331,6 +1446,7 @@ std::vector<int64_t> Engine::validate(int64_t source) {
   comm_.allreduce_sum_i64(out.data(), 3);
   std::vector<int64_t> h(3);
   be_.to_host(h.data(), out.data(), 3 * sizeof(int64_t));
+  check_device();
   return h;
 }
 

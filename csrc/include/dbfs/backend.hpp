@@ -982,16 +982,25 @@ struct ScanBfsArgs {
 // violations of (a) |level[u] - level[v]| <= 1 over every edge with both ends
 // reached, (b) reached-unreached edges, (c) reached v != src without a
 // neighbour at level[v] - 1.  out[0..2] += counts.
+// directed: g is the in-edge view (DeviceGraph::in_view: row v holds the u of
+// every stored entry u -> v) and the rules are the directed ones -- (a) both
+// ends reached and level[v] > level[u] + 1, (b) u reached and v unreached,
+// (c) reached v != src without an entry u -> v at level[v] - 1; the reverse of
+// (a) and (b) is legal.
 struct ValidateArgs {
   ShardView g;
   const lvl_t* level_global = nullptr;  // n entries
   int64_t src = 0;
   int64_t* out = nullptr;               // 3 counters (device)
+  bool directed = false;
 };
 
 // Graph500 parent tree from levels: parent[v] = first neighbour u with
 // level[u] == level[v] - 1 (global vertex id), parent[src] = src, -1 if
 // unreached.  Computed after a run from the all-gathered level array.
+// A directed graph: the caller passes the in-edge view as g (the rule is the
+// same, nothing branches); its rows are in ascending id order, so the parent is
+// the smallest u with an entry u -> v one level closer.
 struct ParentArgs {
   ShardView g;
   const lvl_t* level_global = nullptr;  // n entries
@@ -1024,6 +1033,12 @@ struct MsMailbox {
 // What every ms kernel shares.
 struct MsState {
   ShardView g;
+  // The rows a pull searches: the in-edge shard of a directed graph
+  // (DeviceGraph::in_view), g's own arrays otherwise.  Everything else (push,
+  // settle, the degrees a level's totals sum) stays on g, the out-edges.
+  const eid_t* in_row_off = nullptr;
+  const vid_t* in_col = nullptr;
+  bool directed = false;
   word_t* seen = nullptr;   // owned rows
   word_t* front = nullptr;  // this level's frontier words, by global vertex
   word_t* next = nullptr;   // owned rows: the new bits of this level
@@ -1113,6 +1128,10 @@ struct MsDegreeArgs {
 //     src[s] itself for u == src[s]; all ones when u is unreached (or has no
 //     such neighbour).
 // Entries of sources s >= k are neither counted nor stored.
+// directed: g is the in-edge view (row v: the u of every stored entry u -> v,
+// ascending) and the rules are ValidateArgs' directed ones -- gap: both reached
+// and lvl[v] > lvl[u] + 1; cross: u reached, v unreached; orphan and parent as
+// above over the in-row (the first parent is then the smallest id).
 constexpr int kMsCheckCounters = 3;
 constexpr uint32_t kMsNoParent = 0xFFFFFFFFu;
 struct MsCheckArgs {
@@ -1125,6 +1144,7 @@ struct MsCheckArgs {
   word_t batch_mask = 0;         // bit s set: s < k
   int64_t* out = nullptr;        // kMsSources x kMsCheckCounters, accumulated; nullptr: no counts
   uint32_t* par = nullptr;       // owned rows x kMsSources; nullptr: no parents
+  bool directed = false;
 };
 
 // ---- backend ----------------------------------------------------------------
@@ -1277,7 +1297,9 @@ class Backend {
   virtual void sort_neighbors(const eid_t* row_off, vid_t* col, int64_t rows, const uint32_t* key_deg) = 0;
   // Every row in neighbour-id order (n: vertex count; the device orders rows
   // of more than 4096 entries by 4096 id buckets only).
-  virtual void sort_rows_by_id(const eid_t* row_off, vid_t* col, int64_t rows, int64_t n) = 0;
+  // exact_long: those rows in exact id order too (the in-edge shard).
+  virtual void sort_rows_by_id(const eid_t* row_off, vid_t* col, int64_t rows, int64_t n,
+                               bool exact_long = false) = 0;
   // head[r] = col[row_off[r]] (0 for empty rows); with hub_idx (one entry per
   // vertex, UINT32_MAX for non-hubs) a hub head is stored as kHubFlag | index.
   virtual void row_heads(const eid_t* row_off, const vid_t* col, int64_t rows, vid_t* head,
@@ -1318,6 +1340,12 @@ class Backend {
                                  int64_t* counts) = 0;
   virtual void route_edges_fill(const vid_t* u, const vid_t* v, int64_t m, int64_t part, int nranks,
                                 int64_t* cursor, uint64_t* out) = 0;
+  // In-edge build (DeviceGraph::build_in_edges): every stored entry r -> c of
+  // the shard g (rows [g.lo, g.lo + g.rows)) goes to rank c / part as
+  // (c << 32 | g.lo + r).  counts[p] += entries for rank p; then the entries
+  // scattered into per-rank segments (cursor[p] = segment start, advanced).
+  virtual void in_route_count(const ShardView& g, int64_t part, int nranks, int64_t* counts) = 0;
+  virtual void in_route_fill(const ShardView& g, int64_t part, int nranks, int64_t* cursor, uint64_t* out) = 0;
   virtual void entries_count(const uint64_t* e, int64_t k, int64_t lo, eid_t* deg) = 0;
   virtual void entries_fill(const uint64_t* e, int64_t k, int64_t lo, eid_t* cursor, vid_t* col) = 0;
   // sum of degrees of vertices with level != kUnreached (device scalar out)

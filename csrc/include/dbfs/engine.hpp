@@ -78,6 +78,20 @@ class DeviceGraph {
   // kTdMaxHubs highest-degree vertices encoded; one more nnz x 4 B).
   void sort_neighbors_by_degree(Comm& comm, bool hubs = true, int64_t max_hubs = kMaxHubs, bool id_order = true,
                                 bool td_hubs = true);
+  // The in-edge shard of a directed graph: for every owned vertex v the global
+  // ids u of all stored entries u -> v of the whole graph, duplicates and
+  // self-loops kept, every row in ascending u.  Built on the device from
+  // `col` as it stands (any row order), collective over `comm`, one time: a
+  // second call does nothing.  The owned out-entries are counted per owner of
+  // their target, exchanged as (target << 32 | source) and built into rows by
+  // count -> scan -> fill as from_edges, then sorted by id.  Transient: 16 B
+  // per stored entry (send + receive), freed before return; resident: 4 B per
+  // received entry + 8 B per row.  No heads, row records or hub encoding.
+  void build_in_edges(Comm& comm);
+  bool has_in_edges() const { return has_in_edges_; }
+  // row_off, col, n, lo, rows and nnz of the in-edge shard; everything else unset
+  ShardView in_view() const;
+  HostCSR in_edges_to_host() const;  // the in-edge shard, copied back (tests)
   bool hub_sorted() const { return hub_sorted_; }
   // col is in id order (bottom-up must scan hub_col, whose order is hub-first)
   bool col_by_id() const { return col_by_id_; }
@@ -118,6 +132,10 @@ class DeviceGraph {
   void build_nz_view();
   DBuf<eid_t> row_off_;
   DBuf<vid_t> col_;
+  bool has_in_edges_ = false;
+  int64_t in_nnz_ = 0;
+  DBuf<eid_t> in_row_off_;
+  DBuf<vid_t> in_col_;
 };
 
 struct EngineOptions {
@@ -350,9 +368,11 @@ struct EngineOptions {
   // with one rank: lets a 1-rank RCCL communicator exercise every collective
   // call on a single GPU (tests).
   bool force_exchange = false;
-  // Directed input (CSR holds out-edges only): top-down modes only; vertices
-  // without out-edges are not pre-marked visited; traversed edges = out-edges
-  // of the reached vertices.
+  // Directed input (CSR holds out-edges only): top-down modes only for run();
+  // vertices without out-edges are not pre-marked visited; traversed edges =
+  // out-edges of the reached vertices.  run_batch, validate and the parent
+  // trees build the graph's in-edge shard on their first call
+  // (DeviceGraph::build_in_edges, or Engine::build_in_edges up front).
   bool directed = false;
 };
 
@@ -401,7 +421,11 @@ struct RunResult {
   double ms = 0.0;             // wall time of the traversal (max over ranks)
   int64_t reached = 0;         // vertices reached (global)
   int64_t edges = 0;           // traversed undirected edges (Graph500)
-  int depth = 0;               // number of levels (max level + 1)
+  // number of levels (max level + 1).  A directed graph: the levels expanded
+  // -- one fewer when no vertex of the deepest level has an out-edge (the
+  // frontier counts vertices with edges only); BatchResult::depth counts that
+  // level too.
+  int depth = 0;
   double gteps = 0.0;
   int mispredicts = 0;         // device loop: level chains enqueued for the wrong direction
   std::vector<LevelRecord> levels;
@@ -433,8 +457,12 @@ struct BatchResult {
   // deeper than one-byte levels hold and was rerun
   bool wide_levels = false;
   // per source, in the order given
-  std::vector<int64_t> reached, edges, dist_sum;  // edges: degree sum of the reached / 2
-  std::vector<int> depth;                         // levels (max level + 1)
+  // edges: degree sum of the reached / 2; directed graphs: their out-degree
+  // sum, not halved (RunResult::edges' convention)
+  std::vector<int64_t> reached, edges, dist_sum;
+  // levels (max level + 1), the deepest level counted on a directed graph too
+  // (RunResult::depth there: the levels expanded)
+  std::vector<int> depth;
   std::vector<std::vector<int64_t>> discovered;   // [source][level]
   std::vector<BatchLevelRecord> levels;
   // run_batch(validate): per source, in the order given, the device check's
@@ -449,7 +477,7 @@ struct BatchResult {
 // Fault injection for failure-detection tests (see Engine::inject_fault).
 struct FaultSpec {
   int rank = -1, level = -1;
-  std::string kind = "throw";
+  std::string kind = "throw";  // FaultSpec::from_env lists the kinds
   int ms = 2000;  // kind=delay: how long the rank sleeps before enqueueing the level
   int us = 500;   // kind=late_wg: how long td_sparse's ticket-less workgroups wait (TdSparseArgs::late_ticks)
   static FaultSpec from_env();
@@ -490,6 +518,10 @@ class Engine {
   // The last batch's levels, [k][n] row-major, kUnreached where source k does
   // not reach; collective.  Throws when the batch ran without keep_levels.
   std::vector<lvl_t> gather_batch_levels();
+  // Directed graphs: build the in-edge shard now (collective; a no-op when it
+  // exists or the graph is undirected) instead of on the first call that
+  // needs it.
+  void build_in_edges();
   // The last batch's parent trees, [k][n] row-major, with gather_parents'
   // convention per source (parent[src] = src, -1 unreached); collective.
   // Throws when the batch ran without keep_parents.
@@ -532,6 +564,7 @@ class Engine {
   void gather_levels_device(DBuf<lvl_t>& full);
   bool exchange() const { return part_.nranks > 1 || opt_.force_exchange; }
   void inject_fault(int level);
+  void inject_batch_fault(int level);  // kind=batch_device, at level `level` of a batch pass
   void check_device();
 
   DeviceGraph& g_;
@@ -636,6 +669,9 @@ class Engine {
   // 0: done; 1: deeper than the level type holds (rerun wider)
   int run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out);
   void collect_batch_levels(int64_t first, int k);
+  // the view a level check walks: the in-edge shard of a directed graph
+  // (built on first use), the shard itself otherwise
+  ShardView check_view();
   std::vector<lvl_t> batch_levels_;      // [k][n], passes collected so far
   int64_t batch_k_ = -1;                 // sources of the last batch (-1: none, or without levels)
   int64_t batch_pending_first_ = -1;     // last pass not collected yet: its first source ...

@@ -7,18 +7,12 @@
 // degrees (device atomics), an exclusive scan turns degrees into row offsets,
 // pass 2 regenerates the same edges and scatters them (atomic cursors).  No
 // edge list is ever materialised, so RMAT-27 on 8 GPUs needs only the shard.
-#include <hip/hip_runtime.h>
-
-#include "launch.hpp"
-#include "wave.hpp"
+#include "kernel_common.hpp"
 
 namespace dbfs {
 namespace kern {
 namespace {
 
-using namespace dev;
-
-constexpr int kBlock = 256;
 constexpr int kScanItems = 16;
 constexpr int kScanTile = kBlock * kScanItems;
 
@@ -102,6 +96,104 @@ __global__ __launch_bounds__(kBlock) void route_fill_kernel(const vid_t* __restr
     if (i < m) {
       out[s_base[ra] + ka] = (static_cast<unsigned long long>(a) << 32) | b;
       out[s_base[rb] + kb] = (static_cast<unsigned long long>(b) << 32) | a;
+    }
+    __syncthreads();
+  }
+}
+
+// ---- in-edge build (DeviceGraph::build_in_edges) ------------------------------
+// Every stored entry r -> c of the shard goes to the owner of c as
+// (c << 32 | lo + r).  Both passes split the work by adjacency entries, never
+// by rows (a hub row of millions of entries is so many tiles, not one lane's
+// walk), and count per rank in LDS as the route kernels above.  The count pass
+// needs no rows at all.  The fill pass gives each workgroup a run of
+// consecutive tiles of kBlock entries: it finds the run's first row once by a
+// search in row_off, each tile advances from the tile before (in_row_advance),
+// and a thread finds its entry's row between its tile's first and last row.
+
+// Largest r in [r, hi] with row_off[r] <= e (row_off[r] <= e on entry;
+// row_off[hi + 1] > e): galloping steps, then a binary search.
+__device__ __forceinline__ int64_t in_row_advance(const eid_t* __restrict__ row_off, int64_t r, int64_t hi, eid_t e) {
+  int64_t step = 1;
+  while (r + step <= hi && row_off[r + step] <= e) {
+    r += step;
+    step <<= 1;
+  }
+  int64_t top = min(r + step, hi + 1);  // row_off[top] > e
+  while (top - r > 1) {
+    const int64_t mid = r + ((top - r) >> 1);
+    if (row_off[mid] <= e) r = mid;
+    else top = mid;
+  }
+  return r;
+}
+
+__global__ __launch_bounds__(kBlock) void in_route_count_kernel(ShardView g, int64_t part, int nranks,
+                                                               unsigned long long* __restrict__ counts) {
+  __shared__ unsigned s_cnt[kMaxRouteRanks];
+  __shared__ unsigned long long s_sum[kMaxRouteRanks];
+  for (int r = threadIdx.x; r < nranks; r += kBlock) s_sum[r] = 0ull;
+  // (32-bit LDS counters, flushed into the 64-bit sums before they can wrap)
+  constexpr int64_t kFlush = int64_t(1) << 30;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+  for (int64_t e0 = static_cast<int64_t>(blockIdx.x) * kBlock; e0 < g.nnz; e0 += stride * (kFlush / kBlock)) {
+    for (int r = threadIdx.x; r < nranks; r += kBlock) s_cnt[r] = 0;
+    __syncthreads();
+    const int64_t end = min(g.nnz, e0 + stride * (kFlush / kBlock));
+    for (int64_t e = e0 + threadIdx.x; e < end; e += stride) {
+      const int64_t o = static_cast<int64_t>(g.col[e]) / part;
+      DBFS_DCHECK(o < nranks, 40, g.col[e]);
+      atomicAdd(&s_cnt[o], 1u);
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < nranks; r += kBlock) s_sum[r] += s_cnt[r];
+    __syncthreads();
+  }
+  for (int r = threadIdx.x; r < nranks; r += kBlock)
+    if (s_sum[r]) atomicAdd(counts + r, s_sum[r]);
+}
+
+__global__ __launch_bounds__(kBlock) void in_route_fill_kernel(ShardView g, int64_t part, int nranks,
+                                                              unsigned long long* __restrict__ cursor,
+                                                              unsigned long long* __restrict__ out) {
+  __shared__ unsigned s_cnt[kMaxRouteRanks];
+  __shared__ unsigned long long s_base[kMaxRouteRanks];
+  __shared__ int64_t s_row[2];  // the tile's first and last row
+  // this workgroup's run of consecutive tiles
+  const int64_t tiles = (g.nnz + kBlock - 1) / kBlock;
+  const int64_t per = (tiles + gridDim.x - 1) / gridDim.x;
+  const int64_t tile0 = static_cast<int64_t>(blockIdx.x) * per, tile1 = min(tiles, tile0 + per);
+  int64_t first = 0;  // (thread 0) the row of the tile's first entry
+  if (threadIdx.x == 0 && tile0 < tile1) first = in_row_advance(g.row_off, 0, g.rows - 1, tile0 * kBlock);
+  for (int64_t tile = tile0; tile < tile1; ++tile) {
+    const int64_t t0 = tile * kBlock, tend = min(g.nnz, t0 + kBlock);
+    for (int r = threadIdx.x; r < nranks; r += kBlock) s_cnt[r] = 0;
+    if (threadIdx.x == 0) {
+      first = in_row_advance(g.row_off, first, g.rows - 1, t0);
+      s_row[0] = first;
+      s_row[1] = in_row_advance(g.row_off, first, g.rows - 1, tend - 1);
+    }
+    __syncthreads();
+    const int64_t e = t0 + threadIdx.x;
+    int o = -1;
+    unsigned k = 0;
+    unsigned long long entry = 0;
+    if (e < tend) {
+      const int64_t r = in_row_advance(g.row_off, s_row[0], s_row[1], e);
+      DBFS_DCHECK(r >= 0 && r < g.rows && g.row_off[r] <= e && e < g.row_off[r + 1], 41, e);
+      const vid_t c = g.col[e];
+      o = static_cast<int>(c / part);
+      DBFS_DCHECK(o < nranks, 42, c);
+      k = atomicAdd(&s_cnt[o], 1u);
+      entry = (static_cast<unsigned long long>(c) << 32) | static_cast<unsigned long long>(g.lo + r);
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < nranks; r += kBlock)
+      s_base[r] = s_cnt[r] ? atomicAdd(cursor + r, static_cast<unsigned long long>(s_cnt[r])) : 0ull;
+    __syncthreads();
+    if (e < tend) {
+      DBFS_DCHECK(s_base[o] + k < static_cast<unsigned long long>(g.nnz), 43, s_base[o] + k);
+      out[s_base[o] + k] = entry;
     }
     __syncthreads();
   }
@@ -213,6 +305,25 @@ __device__ __forceinline__ void validate_edge(lvl_t lu, lvl_t lv, long long& gap
   if (lv == lu - 1) parent = true;
 }
 
+// The directed rules over an in-edge row: lv is the row's vertex v, lu the
+// source u of a stored entry u -> v.
+__device__ __forceinline__ void validate_in_edge(lvl_t lv, lvl_t lu, long long& gap, long long& cross, bool& parent) {
+  if (lu == kUnreached) return;  // (an unreached u with a reached v is legal)
+  if (lv == kUnreached) {
+    ++cross;
+    return;
+  }
+  if (lv - lu > 1) ++gap;  // (a back edge to a smaller level is legal)
+  if (lu == lv - 1) parent = true;
+}
+
+template <bool kDirected>
+__device__ __forceinline__ void validate_entry(lvl_t lown, lvl_t lnb, long long& gap, long long& cross, bool& parent) {
+  if (kDirected) validate_in_edge(lown, lnb, gap, cross, parent);
+  else validate_edge(lown, lnb, gap, cross, parent);
+}
+
+template <bool kDirected>
 __global__ __launch_bounds__(kBlock) void validate_kernel(ValidateArgs a) {
   const int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const int lane = lane_id();
@@ -224,7 +335,7 @@ __global__ __launch_bounds__(kBlock) void validate_kernel(ValidateArgs a) {
   long long gap = 0, cross = 0, orphan = 0;
   bool has_parent = false;
   if (valid && !longrow)
-    for (eid_t i = b; i < e; ++i) validate_edge(lu, a.level_global[a.g.col[i]], gap, cross, has_parent);
+    for (eid_t i = b; i < e; ++i) validate_entry<kDirected>(lu, a.level_global[a.g.col[i]], gap, cross, has_parent);
   // long rows: one at a time, the wave's lanes over its entries
   unsigned long long pending = __ballot(valid && longrow);
   while (pending) {
@@ -233,7 +344,8 @@ __global__ __launch_bounds__(kBlock) void validate_kernel(ValidateArgs a) {
     const eid_t lb = __shfl(b, leader, kWave), le = __shfl(e, leader, kWave);
     const lvl_t llu = __shfl(lu, leader, kWave);
     bool par = false;
-    for (eid_t i = lb + lane; i < le; i += kWave) validate_edge(llu, a.level_global[a.g.col[i]], gap, cross, par);
+    for (eid_t i = lb + lane; i < le; i += kWave)
+      validate_entry<kDirected>(llu, a.level_global[a.g.col[i]], gap, cross, par);
     if (__ballot(par) && lane == leader) has_parent = true;
   }
   if (valid) {
@@ -341,6 +453,18 @@ void route_edges_fill(const vid_t* u, const vid_t* v, int64_t m, int64_t part, i
       u, v, m, part, nranks, reinterpret_cast<unsigned long long*>(cursor), reinterpret_cast<unsigned long long*>(out));
 }
 
+void in_route_count(const ShardView& g, int64_t part, int nranks, int64_t* counts, hipStream_t st) {
+  if (g.nnz <= 0 || g.rows <= 0) return;
+  in_route_count_kernel<<<capped_grid(g.nnz, 256 * 16), kBlock, 0, st>>>(
+      g, part, nranks, reinterpret_cast<unsigned long long*>(counts));
+}
+
+void in_route_fill(const ShardView& g, int64_t part, int nranks, int64_t* cursor, uint64_t* out, hipStream_t st) {
+  if (g.nnz <= 0 || g.rows <= 0) return;
+  in_route_fill_kernel<<<capped_grid(g.nnz, 256 * 16), kBlock, 0, st>>>(
+      g, part, nranks, reinterpret_cast<unsigned long long*>(cursor), reinterpret_cast<unsigned long long*>(out));
+}
+
 void entries_count(const uint64_t* e, int64_t k, int64_t lo, eid_t* deg, hipStream_t st) {
   if (k <= 0) return;
   entries_count_kernel<<<capped_grid(k, 256 * 32), kBlock, 0, st>>>(
@@ -354,6 +478,8 @@ void entries_fill(const uint64_t* e, int64_t k, int64_t lo, eid_t* cursor, vid_t
 }
 
 int route_max_ranks() { return kMaxRouteRanks; }
+
+unsigned long long take_check_graph() { return take_check_local(); }
 
 int64_t scan_tmp_elems(int64_t n) {
   int64_t total = 0;
@@ -378,7 +504,9 @@ void exclusive_scan(eid_t* data, int64_t n, eid_t* tmp, hipStream_t st) {
 
 void validate_levels(const ValidateArgs& a, hipStream_t st) {
   if (a.g.rows <= 0) return;
-  validate_kernel<<<static_cast<unsigned>((a.g.rows + kBlock - 1) / kBlock), kBlock, 0, st>>>(a);
+  const unsigned grid = static_cast<unsigned>((a.g.rows + kBlock - 1) / kBlock);
+  if (a.directed) validate_kernel<true><<<grid, kBlock, 0, st>>>(a);
+  else validate_kernel<false><<<grid, kBlock, 0, st>>>(a);
 }
 
 void compute_parents(const ParentArgs& a, hipStream_t st) {

@@ -185,6 +185,70 @@ __global__ __launch_bounds__(kLongThreads) void bucket_long_rows_kernel(const ei
   }
 }
 
+// Rows longer than kMaxLds in exact id order (the in-edge shard, whose rows
+// must be ascending whatever their length): a stable least-significant-digit
+// radix sort, kRadixBits bits a pass, one workgroup per row, between col and
+// `tmp`.  Thread t owns the t-th contiguous chunk of the row and its own
+// column of the digit counters (s_cnt[digit][t]); a scan in digit-major order
+// gives every (digit, thread) its first output slot, so equal digits keep
+// their order.  One-time preprocessing of a handful of rows, not tuned: a
+// thread's chunk is contiguous (its loads and stores do not coalesce), and a
+// very large hub's row -- millions of entries -- is ceil(bits / 4) passes of
+// this one workgroup, not of the grid.
+constexpr int kRadixBits = 4;
+constexpr int kRadix = 1 << kRadixBits;
+
+__global__ __launch_bounds__(kBlock) void radix_long_rows_kernel(const eid_t* __restrict__ ro, vid_t* col,
+                                                                const int64_t* __restrict__ list,
+                                                                const unsigned long long* __restrict__ count,
+                                                                vid_t* tmp, int bits) {
+  __shared__ unsigned s_cnt[kRadix * kBlock];
+  __shared__ unsigned s_wave[kBlock / kWave];
+  const unsigned long long nrows = *count;
+  const int t = threadIdx.x;
+  for (unsigned long long i = blockIdx.x; i < nrows; i += gridDim.x) {
+    const int64_t r = list[i];
+    const eid_t b = ro[r];
+    const int64_t len = ro[r + 1] - b;  // (< 2^32: the counters are 32-bit)
+    const int64_t per = (len + kBlock - 1) / kBlock;
+    const int64_t c0 = min(len, t * per), c1 = min(len, c0 + per);
+    vid_t* src = col + b;
+    vid_t* dst = tmp + b;
+    for (int shift = 0; shift < bits; shift += kRadixBits) {
+#pragma unroll
+      for (int d = 0; d < kRadix; ++d) s_cnt[d * kBlock + t] = 0;
+      for (int64_t x = c0; x < c1; ++x) ++s_cnt[((src[x] >> shift) & (kRadix - 1)) * kBlock + t];
+      __syncthreads();
+      // exclusive scan of the kRadix x kBlock counters (kRadix consecutive per thread)
+      unsigned loc[kRadix], sum = 0;
+#pragma unroll
+      for (int k = 0; k < kRadix; ++k) {
+        loc[k] = sum;
+        sum += s_cnt[t * kRadix + k];
+      }
+      const unsigned incl = static_cast<unsigned>(wave_incl_scan(static_cast<long long>(sum)));
+      if (lane_id() == kWave - 1) s_wave[t >> 6] = incl;
+      __syncthreads();
+      unsigned off = incl - sum;
+      for (int w = 0; w < (t >> 6); ++w) off += s_wave[w];
+#pragma unroll
+      for (int k = 0; k < kRadix; ++k) s_cnt[t * kRadix + k] = off + loc[k];
+      __syncthreads();
+      for (int64_t x = c0; x < c1; ++x) {
+        const vid_t v = src[x];
+        dst[s_cnt[((v >> shift) & (kRadix - 1)) * kBlock + t]++] = v;
+      }
+      __syncthreads();
+      vid_t* const sw = src;
+      src = dst;
+      dst = sw;
+    }
+    if (src != col + b)
+      for (int64_t x = t; x < len; x += kBlock) col[b + x] = src[x];
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void row_heads_kernel(const eid_t* __restrict__ ro, const vid_t* __restrict__ col,
                                                           int64_t rows, vid_t* __restrict__ head,
                                                           const uint32_t* __restrict__ hub_idx) {
@@ -359,7 +423,7 @@ void sort_neighbors(const eid_t* row_off, vid_t* col, int64_t rows, const uint32
 }
 
 void sort_rows_by_id(const eid_t* row_off, vid_t* col, int64_t rows, int64_t n, int64_t* list,
-                     unsigned long long* count, vid_t* tmp, hipStream_t st) {
+                     unsigned long long* count, vid_t* tmp, bool exact_long, hipStream_t st) {
   if (rows <= 0) return;
   sort_neighbors(row_off, col, rows, nullptr, list, count, st);
   int bits = 0;
@@ -368,7 +432,8 @@ void sort_rows_by_id(const eid_t* row_off, vid_t* col, int64_t rows, int64_t n, 
   (void)hipMemsetAsync(count, 0, sizeof(unsigned long long), st);
   list_long_rows_kernel<<<static_cast<unsigned>((rows + kBlock - 1) / kBlock), kBlock, 0, st>>>(row_off, rows, list,
                                                                                                 count);
-  bucket_long_rows_kernel<<<1024, kLongThreads, 0, st>>>(row_off, col, list, count, tmp, shift);
+  if (exact_long) radix_long_rows_kernel<<<1024, kBlock, 0, st>>>(row_off, col, list, count, tmp, bits);
+  else bucket_long_rows_kernel<<<1024, kLongThreads, 0, st>>>(row_off, col, list, count, tmp, shift);
 }
 
 }  // namespace kern

@@ -17,9 +17,12 @@ namespace dbfs {
 namespace kern {
 
 // Checked build: the first violation recorded by the top-down / bottom-up
-// kernel files (cleared); bfs_kernels.hip's take_check_error reads all three.
+// kernel files, the batch kernels and the graph-build kernels (cleared);
+// bfs_kernels.hip's take_check_error reads them all.
 unsigned long long take_check_td();
 unsigned long long take_check_bu();
+unsigned long long take_check_ms();
+unsigned long long take_check_graph();
 // A level's totals and finish from unscanned unit statistics, one workgroup
 // (bfs_kernels.hip; bottom-up levels without the fused finish).
 void totals_finish(const ScanArgs& a, hipStream_t st);

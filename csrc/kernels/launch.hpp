@@ -148,6 +148,10 @@ void route_edges_count(const vid_t* u, const vid_t* v, int64_t m, int64_t part, 
                        hipStream_t st);
 void route_edges_fill(const vid_t* u, const vid_t* v, int64_t m, int64_t part, int nranks, int64_t* cursor,
                       uint64_t* out, hipStream_t st);
+// In-edge build: the shard's stored entries r -> c counted per owner of c and
+// scattered there as (c << 32 | lo + r), as the route passes above.
+void in_route_count(const ShardView& g, int64_t part, int nranks, int64_t* counts, hipStream_t st);
+void in_route_fill(const ShardView& g, int64_t part, int nranks, int64_t* cursor, uint64_t* out, hipStream_t st);
 void entries_count(const uint64_t* e, int64_t k, int64_t lo, eid_t* deg, hipStream_t st);
 void entries_fill(const uint64_t* e, int64_t k, int64_t lo, eid_t* cursor, vid_t* col, hipStream_t st);
 int route_max_ranks();
@@ -175,10 +179,10 @@ void hub_assign(const uint32_t* deg, int64_t n, uint32_t min_deg, const eid_t* c
 // list must hold `rows` entries; count is one device counter
 void sort_neighbors(const eid_t* row_off, vid_t* col, int64_t rows, const uint32_t* key_deg, int64_t* list,
                     unsigned long long* count, hipStream_t st);
-// rows in id order (rows of 2..4096 exactly, longer rows by 4096 id buckets);
-// tmp holds nnz entries
+// rows in id order (rows of 2..4096 exactly, longer rows by 4096 id buckets,
+// or exactly too with exact_long); tmp holds nnz entries
 void sort_rows_by_id(const eid_t* row_off, vid_t* col, int64_t rows, int64_t n, int64_t* list,
-                     unsigned long long* count, vid_t* tmp, hipStream_t st);
+                     unsigned long long* count, vid_t* tmp, bool exact_long, hipStream_t st);
 void reached_degree_sum(const ShardView& g, const lvl_t* level, int64_t* out2, hipStream_t st);
 void degree_moments(const ShardView& g, int64_t* out2, hipStream_t st);
 

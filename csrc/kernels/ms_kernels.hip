@@ -212,11 +212,17 @@ __global__ __launch_bounds__(kWave) void ms_init_kernel(MsInitArgs a) {
   }
 }
 
-template <class L>
+// kDirected: the rows searched are the in-edge shard's (MsState::in_row_off /
+// in_col), and a vertex with new bits is recorded with its out-degree, read
+// from g.row_off only then.  The undirected instantiation reads g's arrays
+// alone, as before the flag existed.
+template <class L, bool kDirected>
 __global__ __launch_bounds__(kMsBlock) void ms_pull_kernel(MsPullArgs a) {
   __shared__ unsigned long long s_tot[kMsStats];
   const MsState& s = a.s;
   const ShardView& g = s.g;
+  const eid_t* row_off = kDirected ? s.in_row_off : g.row_off;
+  const vid_t* col = kDirected ? s.in_col : g.col;
   const int t = threadIdx.x;
   const int lane = lane_id();
   if (t < kMsStats) s_tot[t] = 0ull;
@@ -232,8 +238,8 @@ __global__ __launch_bounds__(kMsBlock) void ms_pull_kernel(MsPullArgs a) {
       sv = s.seen[v];
       need = ~sv & s.batch_mask;
       if (need) {
-        rs = g.row_off[v];
-        re = g.row_off[v + 1];
+        rs = row_off[v];
+        re = row_off[v + 1];
         if (rs == re) need = 0ull;
       }
     }
@@ -241,7 +247,7 @@ __global__ __launch_bounds__(kMsBlock) void ms_pull_kernel(MsPullArgs a) {
     if (need) {
       const eid_t lim = min(re, rs + static_cast<eid_t>(a.lane_limit));
       for (eid_t e = rs; e < lim; ++e) {
-        got |= s.front[g.col[e]];
+        got |= s.front[col[e]];
         if ((got & need) == need) break;
       }
     }
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(kMsBlock) void ms_pull_kernel(MsPullArgs a) {
       const word_t nd = readlane64(need, l);
       word_t x = readlane64(got, l);
       for (eid_t e = b; e < en; e += kWave) {
-        const word_t f = e + lane < en ? s.front[g.col[e + lane]] : 0ull;
+        const word_t f = e + lane < en ? s.front[col[e + lane]] : 0ull;
         x |= wave_or(f);
         if ((x & nd) == nd) break;
       }
@@ -265,7 +271,9 @@ __global__ __launch_bounds__(kMsBlock) void ms_pull_kernel(MsPullArgs a) {
       if (nw) s.seen[v] = sv | nw;
       s.next[v] = nw;
     }
-    ms_record<L>(s, in, v, nw, re - rs, acc);
+    long long deg = re - rs;
+    if (kDirected) deg = nw ? g.row_off[v + 1] - g.row_off[v] : 0;  // (what the next push costs: out-entries)
+    ms_record<L>(s, in, v, nw, deg, acc);
   }
   ms_finish(s, acc, s_tot, false);
 }
@@ -433,7 +441,10 @@ __global__ __launch_bounds__(kMsBlock) void ms_degree_kernel(MsDegreeArgs a) {
 constexpr int kMsCheckGrid = 2048;
 constexpr int kMsCheckAhead = 8;
 
-template <class L, bool kCount, bool kParent>
+// kDirected: g is the in-edge view, lane s holds lvl[v][s] of the row's vertex
+// v and every entry is a u with a stored u -> v: cross = u reached and v not,
+// gap = both reached and lvl[v] > lvl[u] + 1 (MsCheckArgs).
+template <class L, bool kCount, bool kParent, bool kDirected>
 __global__ __launch_bounds__(kMsBlock) void ms_check_kernel(MsCheckArgs a) {
   __shared__ unsigned long long s_cnt[kMsSources * kMsCheckCounters];
   const ShardView& g = a.g;
@@ -481,8 +492,13 @@ __global__ __launch_bounds__(kMsBlock) void ms_check_kernel(MsCheckArgs a) {
           const bool rw = lw[i] != kNone;
           if (kCount) {
             const int d = lu - lw[i];
-            if (valid && on && ru != rw) ++cross;
-            if (valid && ru && rw && (d > 1 || d < -1)) ++gap;
+            if (kDirected) {
+              if (valid && on && rw && !ru) ++cross;
+              if (valid && ru && rw && d > 1) ++gap;
+            } else {
+              if (valid && on && ru != rw) ++cross;
+              if (valid && ru && rw && (d > 1 || d < -1)) ++gap;
+            }
           }
           if (valid && ru && rw && lw[i] + 1 == lu && !has_par) {
             has_par = true;
@@ -508,19 +524,26 @@ __global__ __launch_bounds__(kMsBlock) void ms_check_kernel(MsCheckArgs a) {
   }
 }
 
-template <class L>
+template <class L, bool kDirected>
 void ms_check_launch(const MsCheckArgs& a, hipStream_t st) {
   const unsigned grid = grid_for(a.g.rows, kMsBlock / kWave, kMsCheckGrid);
-  if (a.out && a.par) ms_check_kernel<L, true, true><<<grid, kMsBlock, 0, st>>>(a);
-  else if (a.out) ms_check_kernel<L, true, false><<<grid, kMsBlock, 0, st>>>(a);
-  else ms_check_kernel<L, false, true><<<grid, kMsBlock, 0, st>>>(a);
+  if (a.out && a.par) ms_check_kernel<L, true, true, kDirected><<<grid, kMsBlock, 0, st>>>(a);
+  else if (a.out) ms_check_kernel<L, true, false, kDirected><<<grid, kMsBlock, 0, st>>>(a);
+  else ms_check_kernel<L, false, true, kDirected><<<grid, kMsBlock, 0, st>>>(a);
 }
 
 void ms_check(const MsCheckArgs& a, hipStream_t st) {
   if (a.g.rows <= 0 || (!a.out && !a.par)) return;
-  if (a.lvl_bytes == 2) ms_check_launch<uint16_t>(a, st);
-  else ms_check_launch<uint8_t>(a, st);
+  if (a.directed) {
+    if (a.lvl_bytes == 2) ms_check_launch<uint16_t, true>(a, st);
+    else ms_check_launch<uint8_t, true>(a, st);
+  } else {
+    if (a.lvl_bytes == 2) ms_check_launch<uint16_t, false>(a, st);
+    else ms_check_launch<uint8_t, false>(a, st);
+  }
 }
+
+unsigned long long take_check_ms() { return take_check_local(); }
 
 void ms_init(const MsInitArgs& a, hipStream_t st) {
   if (a.s.lvl_bytes == 2) ms_init_kernel<uint16_t><<<1, kWave, 0, st>>>(a);
@@ -529,8 +552,13 @@ void ms_init(const MsInitArgs& a, hipStream_t st) {
 
 void ms_pull(const MsPullArgs& a, hipStream_t st) {
   const unsigned grid = grid_for(a.s.g.rows, kMsBlock, kMsMaxGrid);
-  if (a.s.lvl_bytes == 2) ms_pull_kernel<uint16_t><<<grid, kMsBlock, 0, st>>>(a);
-  else ms_pull_kernel<uint8_t><<<grid, kMsBlock, 0, st>>>(a);
+  if (a.s.directed) {
+    if (a.s.lvl_bytes == 2) ms_pull_kernel<uint16_t, true><<<grid, kMsBlock, 0, st>>>(a);
+    else ms_pull_kernel<uint8_t, true><<<grid, kMsBlock, 0, st>>>(a);
+  } else {
+    if (a.s.lvl_bytes == 2) ms_pull_kernel<uint16_t, false><<<grid, kMsBlock, 0, st>>>(a);
+    else ms_pull_kernel<uint8_t, false><<<grid, kMsBlock, 0, st>>>(a);
+  }
 }
 
 void ms_push(const MsPushArgs& a, hipStream_t st) {

@@ -607,6 +607,10 @@ PYBIND11_MODULE(_dbfs_native, m) {
            py::arg("hubs") = true, py::arg("max_hubs") = kMaxHubs, py::arg("id_order") = true,
            py::arg("td_hubs") = true,
            py::call_guard<py::gil_scoped_release>())
+      // the in-edge shard of a directed graph (collective, one time)
+      .def("build_in_edges", &DeviceGraph::build_in_edges, py::arg("comm"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("has_in_edges", &DeviceGraph::has_in_edges)
+      .def("in_edges_to_host", &DeviceGraph::in_edges_to_host, py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("col_by_id", &DeviceGraph::col_by_id)
       .def_property_readonly("td_hub_share", &DeviceGraph::td_hub_share)
       .def_property_readonly("hub_sorted", &DeviceGraph::hub_sorted)
@@ -733,6 +737,7 @@ PYBIND11_MODULE(_dbfs_native, m) {
           },
           py::arg("sources"), py::arg("direction") = "auto", py::arg("levels") = true, py::arg("validate") = false,
           py::arg("parents") = false)
+      .def("build_in_edges", &Engine::build_in_edges, py::call_guard<py::gil_scoped_release>())
       .def("gather_batch_parents",
            [](Engine& e) {
              std::vector<int64_t> v;

@@ -64,7 +64,10 @@ class BFSResult:
 class BatchResult:
     """One concurrent traversal from k sources (``BFS.run_batch``), 64 sources
     per pass.  Per source, in the order given: ``reached``, ``edges`` (degree
-    sum of the reached // 2), ``depth`` (levels), ``dist_sum`` (sum of levels
+    sum of the reached // 2; on a directed graph their out-degree sum, not
+    halved), ``depth`` (max level + 1; on a directed graph ``run().depth`` is
+    one lower when no vertex of the deepest level has an out-edge, since a
+    single traversal counts the levels it expanded), ``depth`` (levels), ``dist_sum`` (sum of levels
     over the reached) and ``discovered[s][L]`` (vertices source s found at
     level L).  ``levels``: per level of each pass a tuple (pass, level, form,
     active vertices, their edges, host ms), form 'P' push or 'L' pull.  ``wide_levels``:
@@ -75,8 +78,11 @@ class BatchResult:
     (gap, cross, orphan) of the device check's counts over the directed
     adjacency entries -- both ends reached and more than one level apart, one
     end reached and the other not, a reached vertex other than the source
-    without a neighbour one level closer (or the source not at level 0) -- and
-    ``validated``, True when every count is zero; both None when the check was
+    without a neighbour one level closer (or the source not at level 0); on a
+    directed graph, over every stored entry u -> w: both reached and
+    level[w] > level[u] + 1, u reached and w not, a reached vertex without an
+    in-neighbour one level closer (``utils.validate.directed_levels_violations``)
+    -- and ``validated``, True when every count is zero; both None when the check was
     not asked for.  ``check_ms``: wall time of the per-pass checks (validation
     and parents), which ``ms`` never includes; 0.0 without them."""
 
@@ -118,7 +124,13 @@ class BFS:
         MatrixMarket file with ``read_threads`` host threads and the CSR shard
         is built on its GPU (edges routed to their owners by an all-to-all-v),
         or reads only its rows of a binary CSR cache.  ``sharded=False`` reads
-        the whole file on every rank (the reference's bfs_mpi.cu:815 pattern)."""
+        the whole file on every rank (the reference's bfs_mpi.cu:815 pattern).
+
+        ``directed=True`` keeps the pairs as u -> v edges.  ``run`` then needs a
+        top-down mode (``bu`` and ``do`` raise); ``run_batch``, ``validate``
+        and ``parents`` work on the graph's in-edge shard, which the first of
+        them builds on the device (``build_in_edges`` pays for it up front).  A
+        directed file is read whole on every rank."""
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}")
         self.rt = runtime or init_runtime()
@@ -148,6 +160,13 @@ class BFS:
                                force_exchange=force_exchange)
         if directed:  # the CSR holds out-edges only (see build_csr / read_graph)
             self.engine.set_option("directed", 1)
+
+    def build_in_edges(self) -> None:
+        """Directed graphs: build the in-edge shard now (collective, one time;
+        4 bytes per stored entry + 8 per vertex on the device) instead of in
+        the first run_batch / validate / parents call.  Nothing happens, and
+        nothing is allocated, on an undirected graph."""
+        self.engine.build_in_edges()
 
     def use_comm(self, comm) -> None:
         """Rebuild the engine on another communicator (same shard, same
@@ -186,7 +205,9 @@ class BFS:
         """One concurrent traversal from all ``sources`` (64 per pass, one bit
         per source in a 64-bit word per vertex); collective like run().
         ``direction``: "auto" picks push or pull per level (one rank; several
-        ranks always pull), "push" / "pull" / "alternate" force a form.
+        ranks always pull), "push" / "pull" / "alternate" force a form.  On a
+        directed graph a push follows out-edges and a pull searches the
+        in-edge shard (build_in_edges; built here on first use, untimed).
         ``levels=False`` keeps no level matrix (64 bytes per vertex on the
         device): the totals are the same, batch_levels() then raises.  The
         single-source state of run() is left alone.
@@ -214,7 +235,8 @@ class BFS:
         """Parent trees of the last run_batch(parents=True) as int64 [k, n]:
         row i is source i's tree with the convention of parents() (a neighbour
         one level closer, the first in the stored row; parent[source] = source;
-        -1 unreached); collective.  k x n x 8 bytes on the host."""
+        -1 unreached; a directed graph: the smallest in-neighbour one level
+        closer); collective.  k x n x 8 bytes on the host."""
         return self.engine.gather_batch_parents()
 
     def levels(self) -> np.ndarray:
@@ -228,13 +250,16 @@ class BFS:
         """Graph500 parent tree of the last run from ``source`` (collective).
 
         parent[v] is a neighbour one level closer to the source (global vertex
-        id), parent[source] = source, -1 for unreached vertices.  The reference
+        id; on a directed graph the smallest u with an edge u -> v one level
+        closer), parent[source] = source, -1 for unreached vertices.  The reference
         records edge indices as parents and never gathers them (bfs.cu:147,439).
         """
         return self.engine.gather_parents(int(source))
 
     def validate(self, source: int) -> bool:
-        """Graph500-style level validation of the last run on the device (collective)."""
+        """Graph500-style level validation of the last run on the device
+        (collective); a directed graph is checked by the directed rules
+        (``utils.validate.directed_levels_violations``)."""
         gap, cross, orphan = self.engine.validate(int(source))
         return gap == 0 and cross == 0 and orphan == 0
 

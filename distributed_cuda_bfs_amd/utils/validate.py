@@ -74,6 +74,52 @@ def batch_levels_violations(csr, levels_row, src: int) -> Tuple[int, int, int]:
     return gap, cross, int(np.count_nonzero(lone))
 
 
+def directed_levels_violations(csr, levels_row, src: int) -> Tuple[int, int, int]:
+    """(gap, cross, orphan) of one source's levels on a directed CSR (out-edges
+    only), counted exactly as the device check counts them on a directed
+    engine.  Over every stored entry u -> w, duplicates and self-loops
+    included: cross = u reached and w unreached (the reverse is legal); gap =
+    both reached and level[w] > level[u] + 1 (a back edge is legal); orphan =
+    reached vertices v other than ``src`` without an entry u -> v with
+    level[u] == level[v] - 1, plus one if ``src`` is not at level 0 (unreached
+    included).  All zero exactly when the levels are the BFS distances."""
+    lv = np.asarray(levels_row, dtype=np.int64)
+    ro = np.asarray(csr.row_off)
+    w = np.asarray(csr.col).astype(np.int64)
+    n = lv.size
+    u = np.repeat(np.arange(n), np.diff(ro))
+    lu, lw = lv[u], lv[w]
+    ru, rw = lu != UNREACHED, lw != UNREACHED
+    both = ru & rw
+    cross = int(np.count_nonzero(ru & ~rw))
+    gap = int(np.count_nonzero(both & (lw > lu + 1)))
+    has_parent = np.zeros(n, dtype=bool)
+    has_parent[w[both & (lu == lw - 1)]] = True
+    lone = (lv != UNREACHED) & ~has_parent
+    lone[src] = lv[src] != 0
+    return gap, cross, int(np.count_nonzero(lone))
+
+
+def directed_first_parents(csr, levels_row, src: int) -> np.ndarray:
+    """The parent tree the device derives from one source's levels on a directed
+    CSR, int64[n]: parent[v] = the smallest u with a stored entry u -> v and
+    level[u] == level[v] - 1, parent[src] = src, -1 for unreached vertices (and
+    for a reached one without such an entry)."""
+    lv = np.asarray(levels_row, dtype=np.int64)
+    ro = np.asarray(csr.row_off)
+    w = np.asarray(csr.col).astype(np.int64)
+    n = lv.size
+    u = np.repeat(np.arange(n), np.diff(ro))
+    lu, lw = lv[u], lv[w]
+    m = (lu != UNREACHED) & (lw != UNREACHED) & (lu == lw - 1)
+    par = np.full(n, n, dtype=np.int64)
+    np.minimum.at(par, w[m], u[m])
+    par[par == n] = -1
+    par[lv == UNREACHED] = -1
+    par[src] = src
+    return par
+
+
 def parents_are_valid(csr, levels, parents, src: int) -> bool:
     """Graph500 parent-tree check: every reached v != src has an edge to
     parent[v] and level[parent[v]] == level[v] - 1; unreached have -1."""

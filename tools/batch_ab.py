@@ -2,7 +2,7 @@
 """Same-process A/B of the concurrent multi-source BFS against 64 single
 traversals, on one GPU:
 
-    python3 tools/batch_ab.py [--scales 20 22 24 26] [--no-lj] [--no-grid] [--reps 5]
+    python3 tools/batch_ab.py [--scales 20 22 24 26] [--no-lj] [--no-grid] [--reps 5] [--directed]
 
 Per graph: 64 roots from sample_roots(64, seed=5202611); after a warm-up of
 both, run_many(roots) (sum of ms; the baseline) and run_batch(roots,
@@ -14,11 +14,16 @@ matrix and every source must come back clean (its time, check_ms, is printed
 too).  Then one
 forced-push and one forced-pull batch, level by level: a level's active set is
 the same in both, so the table shows where each form is cheaper -- what the
-direction constants (csrc/engine/batch.cpp) are chosen from."""
+direction constants (csrc/engine/batch.cpp) are chosen from.
+
+--directed: the RMAT graphs of --scales as directed graphs instead (the
+generator's pairs as u -> v, the CSR built on the host; no other graph), the
+baseline run_many in mode td; the time of build_in_edges is printed first."""
 import argparse
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -33,14 +38,17 @@ ap.add_argument("--no-grid", action="store_true")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--device", default="hip")
 ap.add_argument("--form-table-max-levels", type=int, default=24)
+ap.add_argument("--directed", action="store_true")
 args = ap.parse_args()
 rt = init_runtime(args.device)
 
 graphs = [(f"rmat{s}_ef16", dbfs.rmat_params(s, 16, 1)) for s in args.scales]
-if not args.no_lj:
+if args.directed:
+    graphs = [(f"directed rmat{s}_ef16 (u -> v)", dbfs.rmat_params(s, 16, 1)) for s in args.scales]
+elif not args.no_lj:
     n, m, _ = LJ_SIZED_POWER_LAW
     graphs.append((f"uniform_{n}_{m} (soc-LiveJournal1's size)", dbfs.uniform_params(n, m, 101)))
-if not args.no_grid:
+if not args.no_grid and not args.directed:
     graphs.append(("grid_1024x1024 (road-like)", dbfs.grid_params(1024, 1024)))
 
 
@@ -50,7 +58,15 @@ def spread(xs):
 
 print(f"# concurrent multi-source BFS vs run_many, {rt.backend.name}, {args.reps} alternating repetitions", flush=True)
 for name, params in graphs:
-    bfs = dbfs.BFS(params, rt, mode="do")
+    if args.directed:
+        u, v = dbfs.generate_edges(params)
+        bfs = dbfs.BFS(dbfs.build_csr(params.n, u, v, directed=True), rt, mode="td", directed=True)
+        del u, v
+        t0 = time.perf_counter()
+        bfs.build_in_edges()
+        print(f"\n{name}: build_in_edges {(time.perf_counter() - t0) * 1e3:.3f} ms", flush=True)
+    else:
+        bfs = dbfs.BFS(params, rt, mode="do")
     roots = bfs.sample_roots(64, seed=5202611)
     E = bfs.engine.global_directed_edges
     many = bfs.run_many(roots)  # warm-up of both
@@ -62,7 +78,10 @@ for name, params in graphs:
         batch = bfs.run_batch(roots, levels=False)
         t_batch.append(batch.ms)
         for i, r in enumerate(many):
-            assert (r.reached, r.edges, r.depth) == (batch.reached[i], batch.edges[i], batch.depth[i]), \
+            assert (r.reached, r.edges, r.depth) == (batch.reached[i], batch.edges[i], batch.depth[i]) or (
+                # a directed run() counts the levels it expanded: one fewer than the batch's
+                # levels when no vertex of the deepest level has an out-edge
+                args.directed and (r.reached, r.edges, r.depth + 1) == (batch.reached[i], batch.edges[i], batch.depth[i])), \
                 (name, roots[i], (r.reached, r.edges, r.depth), (batch.reached[i], batch.edges[i], batch.depth[i]))
     checked = bfs.run_batch(roots, validate=True)
     assert checked.validated, (name, [(roots[i], v) for i, v in enumerate(checked.violations) if v != (0, 0, 0)])
