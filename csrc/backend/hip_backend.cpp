@@ -337,6 +337,8 @@ class HipBackend final : public Backend {
   void nz_fill(const eid_t* ro, const vid_t* head, int64_t rows, const eid_t* pref, eid_t* nz_ro,
                vid_t* nz_head) override {
     on();
+    // a shard without rows: the view's closing offset (the kernel's last word writes it otherwise)
+    if (rows <= 0) HIP_CHECK(hipMemsetAsync(nz_ro, 0, sizeof(eid_t), st_));
     kern::nz_fill(ro, head, rows, div_up(rows, kWordBits), pref, nz_ro, nz_head, st_);
     chk();
   }

@@ -424,6 +424,43 @@ std::vector<uint16_t> DeviceGraph::debug_nz_loc() const {
   return out;
 }
 
+DeviceGraph::DebugTables DeviceGraph::debug_tables() const {
+  be_->synchronize();
+  DebugTables t;
+  const auto copy = [this](auto& out, const auto& buf, int64_t count) {
+    out.clear();
+    if (!buf.data() || count <= 0) return;
+    DBFS_CHECK(static_cast<size_t>(count) <= buf.size(), "debug_tables: a table is shorter than its count");
+    out.resize(static_cast<size_t>(count));
+    be_->to_host(out.data(), buf.data(), out.size() * sizeof(out[0]));
+  };
+  copy(t.hub_vertex, hub_vertex_, nhubs_);
+  copy(t.hub_deg, hub_deg_, nhubs_);
+  copy(t.hub_bits, hub_bits_, part_.global_words());
+  copy(t.hub_col, hub_col_, nnz_);
+  t.td_nhubs = td_nhubs_;
+  copy(t.td_col, td_col_, nnz_);
+  copy(t.td_hub_vertex, td_hub_vertex_, td_nhubs_);
+  copy(t.head, head_, rows_);
+  const int64_t words = div_up(std::max<int64_t>(rows_, 1), kWordBits);
+  copy(t.nz_pref, nz_pref_, words + 1);
+  const int64_t nzrows = t.nz_pref.empty() ? 0 : t.nz_pref.back();
+  copy(t.nz_row_off, nz_row_off_, nzrows + 1);
+  copy(t.nz_head, nz_head_, nzrows);
+  if (nz_rec_.data() && nzrows > 0) {
+    std::vector<NzRec> rec(static_cast<size_t>(nzrows));
+    DBFS_CHECK(rec.size() <= nz_rec_.size(), "debug_tables: a table is shorter than its count");
+    be_->to_host(rec.data(), nz_rec_.data(), rec.size() * sizeof(NzRec));
+    for (const NzRec& r : rec) {
+      t.nz_rec_off.push_back(r.off);
+      t.nz_rec_head.push_back(r.head);
+    }
+  }
+  copy(t.nz_loc, nz_loc_, nzrows);
+  if (rows_ > 0) copy(t.unit_base, unit_base_, div_up(rows_, kUnitVertices) + 1);
+  return t;
+}
+
 void DeviceGraph::debug_drop_records() {
   be_->synchronize();
   nz_rec_ = DBuf<NzRec>();
@@ -1429,6 +1466,17 @@ std::vector<int64_t> Engine::gather_parents(int64_t source) {
   be_.to_host(h.data(), recv.data(), h.size() * sizeof(int64_t));
   h.resize(static_cast<size_t>(part_.n));
   return h;
+}
+
+void Engine::debug_set_level(int64_t vertex, int level) {
+  DBFS_CHECK(vertex >= 0 && vertex < part_.n, "debug_set_level: vertex out of range");
+  DBFS_CHECK(level < kUnreached, "debug_set_level: level out of range");
+  ensure_wide_levels();
+  const int64_t r = vertex - g_.lo();
+  if (r < 0 || r >= g_.rows()) return;  // another rank's
+  const lvl_t x = level < 0 ? kUnreached : static_cast<lvl_t>(level);
+  be_.synchronize();
+  be_.to_device(level_.data() + r, &x, sizeof(x));
 }
 
 std::vector<int64_t> Engine::validate(int64_t source) {

@@ -67,6 +67,21 @@ class DeviceGraph {
   // as if a unit spanned 2^32 edges -- bottom-up then reads the non-empty-row
   // view and no level is hub-cut.  Call it on every rank, before the first run.
   void debug_drop_records();
+  // Debug / tests: host copies of this rank's derived tables (ShardView), an
+  // absent table empty: hub_vertex / hub_deg (nhubs entries), hub_bits
+  // (Partition::global_words()), hub_col and td_col (nnz), td_hub_vertex
+  // (td_nhubs entries), head (rows), nz_pref (words + 1), nz_row_off (non-empty
+  // rows + 1), nz_head, nz_rec_off / nz_rec_head (NzRec's two fields), nz_loc,
+  // unit_base (units + 1).  row_off and col: to_host().
+  struct DebugTables {
+    std::vector<vid_t> hub_vertex, hub_col, td_col, td_hub_vertex, head, nz_head, nz_rec_head;
+    std::vector<uint32_t> hub_deg, nz_rec_off;
+    std::vector<word_t> hub_bits;
+    std::vector<eid_t> nz_pref, nz_row_off, unit_base;
+    std::vector<uint16_t> nz_loc;
+    int64_t td_nhubs = 0;
+  };
+  DebugTables debug_tables() const;
   // Reorder every row hub-first (neighbour degree descending); collective over
   // `comm` (all ranks need every vertex's degree).  One-time preprocessing.
   // With `hubs`, the (up to kMaxHubs) highest-degree vertices of the graph are
@@ -535,6 +550,10 @@ class Engine {
   // resident level matrix (on its owner; level < 0: unreached), so a test can
   // plant a violation for validate_batch_pass to find.
   void debug_set_batch_level(int slot, int64_t vertex, int level);
+  // Test hook: overwrite the last run's level of global `vertex` (on its
+  // owner; level < 0: unreached), so a test can plant a violation for
+  // validate() and parents_local() to find.
+  void debug_set_level(int64_t vertex, int level);
   int64_t batch_sources() const { return batch_k_; }  // of the last batch with levels (-1: none)
   int64_t global_directed_edges() const { return total_directed_; }
   const EngineOptions& options() const { return opt_; }

@@ -114,6 +114,9 @@ PYBIND11_MODULE(_dbfs_native, m) {
   m.attr("TD_EDGES_PER_BLOCK") = py::int_(kTdEdgesPerBlock);
   m.attr("UNIT_VERTICES") = py::int_(kUnitVertices);
   m.attr("MAX_HUBS") = py::int_(kMaxHubs);
+  m.attr("SORTED_ROW_MAX") = py::int_(kSortedRowMax);
+  m.attr("HUB_FLAG") = py::int_(kHubFlag);
+  m.attr("TD_MAX_HUBS") = py::int_(kTdMaxHubs);
   m.attr("SCAN_CHUNK") = py::int_(kScanChunk);
   m.attr("FOLD_SCAN_UNITS") = py::int_(kFoldScanUnits);
   m.attr("MAX_FUSED_GRID") = py::int_(kMaxFusedGrid);
@@ -260,7 +263,26 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def_property_readonly("device_bytes", &Backend::device_bytes)
       .def_property_readonly("peak_device_bytes", &Backend::peak_device_bytes)
       .def_property_readonly("is_gpu", [](const Backend& b) { return b.kind() == DeviceKind::HIP; })
-      .def("synchronize", &Backend::synchronize, py::call_guard<py::gil_scoped_release>());
+      .def("synchronize", &Backend::synchronize, py::call_guard<py::gil_scoped_release>())
+      // debug: Backend::exclusive_scan of `values` in a device buffer of n + 1 elements (element n: the total)
+      .def("debug_exclusive_scan",
+           [](Backend& be, py::array_t<int64_t, py::array::c_style | py::array::forcecast> values) {
+             const size_t n = static_cast<size_t>(values.size());
+             py::array_t<int64_t> out(static_cast<py::ssize_t>(n + 1));
+             const int64_t* src = values.data();
+             int64_t* dst = out.mutable_data();
+             {
+               py::gil_scoped_release nogil;
+               DBuf<eid_t> buf(be, n + 1);
+               be.memset_async(buf.data(), 0, buf.bytes());
+               if (n) be.to_device(buf.data(), src, n * sizeof(eid_t));
+               be.exclusive_scan(buf.data(), static_cast<int64_t>(n));
+               be.to_host(dst, buf.data(), (n + 1) * sizeof(eid_t));
+               be.synchronize();
+             }
+             return out;
+           },
+           py::arg("values"));
   m.def("cpu_backend", []() { return std::shared_ptr<Backend>(make_cpu_backend()); });
   m.def("hip_backend", [](int dev) { return std::shared_ptr<Backend>(make_hip_backend(dev)); }, py::arg("device") = 0);
   m.def("hip_device_count", &hip_device_count);
@@ -628,6 +650,31 @@ PYBIND11_MODULE(_dbfs_native, m) {
         if (!v.empty()) std::memcpy(out.mutable_data(), v.data(), v.size() * sizeof(uint16_t));
         return out;
       })
+      // debug: this rank's derived tables as numpy arrays (an absent table: empty)
+      .def("debug_tables", [](const DeviceGraph& g) {
+        DeviceGraph::DebugTables t;
+        {
+          py::gil_scoped_release nogil;
+          t = g.debug_tables();
+        }
+        py::dict d;
+        d["hub_vertex"] = to_numpy(t.hub_vertex);
+        d["hub_deg"] = to_numpy(t.hub_deg);
+        d["hub_bits"] = to_numpy(t.hub_bits);
+        d["hub_col"] = to_numpy(t.hub_col);
+        d["td_col"] = to_numpy(t.td_col);
+        d["td_hub_vertex"] = to_numpy(t.td_hub_vertex);
+        d["td_nhubs"] = t.td_nhubs;
+        d["head"] = to_numpy(t.head);
+        d["nz_pref"] = to_numpy(t.nz_pref);
+        d["nz_row_off"] = to_numpy(t.nz_row_off);
+        d["nz_head"] = to_numpy(t.nz_head);
+        d["nz_rec_off"] = to_numpy(t.nz_rec_off);
+        d["nz_rec_head"] = to_numpy(t.nz_rec_head);
+        d["nz_loc"] = to_numpy(t.nz_loc);
+        d["unit_base"] = to_numpy(t.unit_base);
+        return d;
+      })
       // debug: release the packed row records (every rank, before the first run)
       .def("debug_drop_records", &DeviceGraph::debug_drop_records);
 
@@ -769,6 +816,8 @@ PYBIND11_MODULE(_dbfs_native, m) {
       // test hook: one entry of the resident level matrix (level < 0: unreached)
       .def("debug_set_batch_level", &Engine::debug_set_batch_level, py::arg("slot"), py::arg("vertex"),
            py::arg("level"), py::call_guard<py::gil_scoped_release>())
+      .def("debug_set_level", &Engine::debug_set_level, py::arg("vertex"), py::arg("level"),
+           py::call_guard<py::gil_scoped_release>())
       .def("gather_batch_levels",
            [](Engine& e) {
              std::vector<lvl_t> v;
