@@ -345,6 +345,73 @@ class CpuBackend final : public Backend {
       }
     }
   }
+  // ---- path counts and dependencies (backend.hpp MsBcArgs): plain loops, every
+  // sum in the kernels' order (stored row order per source, the lanes' tree) ----
+  static int bc_level(const MsBcArgs& a, int64_t v, int s) {
+    const int64_t i = v * kMsSources + s;
+    return a.lvl_bytes == 2 ? static_cast<const uint16_t*>(a.lvl)[i] : static_cast<const uint8_t*>(a.lvl)[i];
+  }
+  static double bc_row_sum(const MsBcArgs& a, int64_t r, int s, int want) {
+    const int none = a.lvl_bytes == 2 ? kMsUnreached16 : kMsUnreached8;
+    double sum = 0.0;
+    if (want == none) return sum;
+    for (eid_t e = a.row_off[r]; e < a.row_off[r + 1]; ++e) {
+      const vid_t w = a.col[e];
+      if (bc_level(a, w, s) == want) sum += a.val[static_cast<int64_t>(w) * kMsSources + s];
+    }
+    return sum;
+  }
+  void ms_bc_init(const MsBcArgs& a) override {
+    for (int s = 0; s < kMsSources; ++s) {
+      const int64_t src = s < a.k ? a.src[s] : -1;
+      for (int64_t v = 0; v < a.lvl_rows; ++v) a.val[v * kMsSources + s] = v == src ? 1.0 : 0.0;
+      for (int64_t r = 0; r < a.g.rows; ++r) a.own[r * kMsSources + s] = a.g.lo + r == src ? 1.0 : 0.0;
+    }
+  }
+  // (the host loops walk every row themselves, the listed long ones included)
+  void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
+                       unsigned long long* count) override {
+    for (int64_t r = 0; r < rows; ++r) {
+      if (row_off[r + 1] - row_off[r] <= above) continue;
+      if (static_cast<int64_t>(*count) < cap) list[*count] = static_cast<vid_t>(r);
+      ++*count;
+    }
+  }
+  void ms_bc_forward(const MsBcArgs& a) override {
+    for (int64_t r = 0; r < a.g.rows; ++r) {
+      bool any = false;
+      for (int s = 0; s < a.k; ++s) {
+        if (bc_level(a, a.g.lo + r, s) != a.level) continue;
+        any = true;
+        a.own[r * kMsSources + s] = bc_row_sum(a, r, s, a.level - 1);
+      }
+      if (any && a.walked) ++*a.walked;
+    }
+  }
+  void ms_bc_backward(const MsBcArgs& a) override {
+    for (int64_t r = 0; r < a.g.rows; ++r) {
+      const int64_t v = a.g.lo + r;
+      double lane[kMsSources] = {};
+      bool any = false, counts = false;
+      for (int s = 0; s < a.k; ++s) {
+        if (bc_level(a, v, s) != a.level) continue;
+        any = true;
+        const double acc = a.leaf ? 0.0 : bc_row_sum(a, r, s, a.level + 1);
+        const double sigma = a.own[r * kMsSources + s];
+        const double delta = sigma * acc;
+        a.own[r * kMsSources + s] = (1.0 + delta) / sigma;
+        if (v != a.src[s]) {
+          lane[s] = delta;
+          counts = true;
+        }
+      }
+      if (any && a.walked) ++*a.walked;
+      if (!counts) continue;
+      for (int off = kMsSources / 2; off > 0; off >>= 1)
+        for (int i = 0; i < off; ++i) lane[i] += lane[i + off];
+      a.dep[r] += lane[0];
+    }
+  }
   void* alloc_mapped(size_t bytes, void** dptr) override {
     void* h = std::calloc(1, std::max<size_t>(bytes, 1));
     DBFS_CHECK(h != nullptr, "host allocation failed");

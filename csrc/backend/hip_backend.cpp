@@ -274,6 +274,15 @@ class HipBackend final : public Backend {
   void ms_settle(const MsSettleArgs& a) override { on(); kern::ms_settle(a, st_); chk(); }
   void ms_degree_sums(const MsDegreeArgs& a) override { on(); kern::ms_degree_sums(a, st_); chk(); }
   void ms_check(const MsCheckArgs& a) override { on(); kern::ms_check(a, st_); chk(); }
+  void ms_bc_init(const MsBcArgs& a) override { on(); kern::ms_bc_init(a, st_); chk(); }
+  void ms_bc_forward(const MsBcArgs& a) override { on(); kern::ms_bc_forward(a, st_); chk(); }
+  void ms_bc_backward(const MsBcArgs& a) override { on(); kern::ms_bc_backward(a, st_); chk(); }
+  void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
+                       unsigned long long* count) override {
+    on();
+    kern::ms_bc_long_rows(row_off, rows, above, list, cap, count, st_);
+    chk();
+  }
   void td_expand(const TdArgs& a) override { on(); kern::td_expand(a, st_); chk(); }
   void td_binned(const BinArgs& a) override { on(); kern::td_binned(a, st_); chk(); }
   void pack_bytes(const PackArgs& a) override { on(); kern::pack_bytes(a, st_); chk(); }

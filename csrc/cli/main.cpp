@@ -26,6 +26,7 @@
 // device (several ranks sharing a GPU: tests).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -59,6 +60,8 @@ struct Args {
   int roots = 0;
   bool batch = false;                 // --roots K: the K roots as one concurrent traversal (Engine::run_batch)
   std::string batch_dir = "auto";
+  bool betweenness = false;           // --batch --betweenness: path counts and dependencies after every pass
+  std::string betweenness_out;        // ... the raw dependency sums, one %.17g per vertex
   bool oracle = true;
   bool validate = false;
   std::string levels_out;
@@ -83,6 +86,8 @@ struct Args {
                "       --roots K (random sources, GTEPS summary)  --no-oracle  --validate\n"
                "       --batch (the K roots concurrently, 64 per pass)  --batch-direction auto|push|pull|alternate\n"
                "       --batch --validate (every pass's levels checked on the device, all its sources at once)\n"
+               "       --batch --betweenness [--betweenness-out FILE] (betweenness centrality of the K roots on the device:\n"
+               "                   the raw dependency sums, checked against the sequential oracle unless --no-oracle)\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only; --batch and --validate work on the in-edge shard,\n"
@@ -126,6 +131,8 @@ Args parse(int argc, char** argv) {
     else if (s == "--roots") a.roots = std::stoi(next());
     else if (s == "--batch") a.batch = true;
     else if (s == "--batch-direction") a.batch_dir = next();
+    else if (s == "--betweenness") a.betweenness = true;
+    else if (s == "--betweenness-out") a.betweenness_out = next();
     else if (s == "--no-oracle") a.oracle = false;
     else if (s == "--validate") a.validate = true;
     else if (s == "--levels-out") a.levels_out = next();
@@ -155,6 +162,9 @@ Args parse(int argc, char** argv) {
     a.src_given = true;
   }
   if (a.gpus < 1) usage("--gpus must be >= 1");
+  if ((a.betweenness || !a.betweenness_out.empty()) && !(a.batch && a.roots > 0))
+    usage("--betweenness needs --roots K --batch");
+  if (!a.betweenness_out.empty() && !a.betweenness) usage("--betweenness-out needs --betweenness");
   if (a.directed) {
     // a single-source traversal is top-down only (the bottom-up kernels take
     // their degrees from their own rows); --batch pulls over the in-edge shard
@@ -601,10 +611,16 @@ int main(int argc, char** argv) {
       const BatchDirection bdir = parse_batch_direction(a.batch_dir);
       std::vector<BatchResult> bres(static_cast<size_t>(nlocal));
       std::vector<lvl_t> blv;
+      std::vector<double> bdep;
       if (!roots.empty())
         run_ranks(ranks, [&](int i, RankCtx& rc) {
-          // (--validate: the device check reads the level matrix, oracle or not)
-          bres[i] = rc.engine->run_batch(roots, bdir, a.oracle || a.validate, a.validate);
+          // (--validate, --betweenness: they read the level matrix, oracle or not)
+          bres[i] = rc.engine->run_batch(roots, bdir, a.oracle || a.validate || a.betweenness, a.validate, false,
+                                         a.betweenness, false);
+          if (a.betweenness) {
+            std::vector<double> d = rc.engine->gather_betweenness();
+            if (i == 0) bdep = std::move(d);
+          }
           if (!a.oracle) return;
           std::vector<lvl_t> lv = rc.engine->gather_batch_levels();
           if (i == 0) blv = std::move(lv);
@@ -639,12 +655,44 @@ int main(int argc, char** argv) {
           std::printf("batch validation %zu/%zu sources clean gap %lld cross %lld orphan %lld\n", clean, roots.size(),
                       viol[0], viol[1], viol[2]);
         }
+        if (a.betweenness) {
+          size_t top = 0;
+          for (size_t v = 1; v < bdep.size(); ++v)
+            if (bdep[v] > bdep[top]) top = v;
+          std::printf("batch betweenness sources %zu bc_ms %.3f max vertex %zu score %.17g\n", roots.size(), b.bc_ms, top,
+                      bdep.empty() ? 0.0 : bdep[top]);
+          if (!a.betweenness_out.empty()) {
+            std::FILE* f = std::fopen(a.betweenness_out.c_str(), "w");
+            DBFS_CHECK(f != nullptr, "cannot write " + a.betweenness_out);
+            for (double x : bdep) std::fprintf(f, "%.17g\n", x);
+            std::fclose(f);
+          }
+          if (check) {
+            // the sequential oracle: relative error 1e-9, an exact 0 where it has one
+            const std::vector<double> exp = cpu_betweenness(full, roots, a.directed).dep;
+            for (size_t v = 0; v < exp.size(); ++v) {
+              const double g = bdep[v], e = exp[v];
+              const bool ok = std::isfinite(g) && (e == 0.0 ? g == 0.0 : std::fabs(g - e) <= 1e-9 * std::fabs(e));
+              if (!ok) {
+                std::printf("betweenness %zu %.17g %.17g\n", v, g, e);
+                std::printf("Wrong output!\n");
+                return 1;
+              }
+            }
+            if (!a.quiet) std::printf("Betweenness OK!\n");
+          }
+        }
         if (a.json) {
           std::string extra;
+          if (a.betweenness) {
+            char ms[64];
+            std::snprintf(ms, sizeof(ms), "%.6f", b.bc_ms);
+            extra = std::string(",\"bc_ms\":") + ms;
+          }
           if (a.validate) {
             char ms[64];
             std::snprintf(ms, sizeof(ms), "%.6f", b.check_ms);
-            extra = ",\"validated_sources\":\"" + std::to_string(clean) + "/" + std::to_string(roots.size()) +
+            extra += ",\"validated_sources\":\"" + std::to_string(clean) + "/" + std::to_string(roots.size()) +
                     "\",\"check_ms\":" + ms;
           }
           std::printf("{\"graph\":\"%s\",\"n\":%lld,\"ranks\":%d,\"batch\":true,\"roots\":%zu,\"passes\":%d,\"ms\":%.6f,"

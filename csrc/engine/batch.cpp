@@ -255,9 +255,11 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
 }
 
 BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirection dir, bool keep_levels, bool validate,
-                              bool keep_parents) {
+                              bool keep_parents, bool betweenness, bool keep_path_counts) {
   DBFS_CHECK(keep_levels || !(validate || keep_parents),
              "run_batch: validate and keep_parents read the level matrix (keep_levels)");
+  DBFS_CHECK(keep_levels || !(betweenness || keep_path_counts),
+             "run_batch: betweenness and keep_path_counts read the level matrix (keep_levels)");
   DBFS_CHECK(!sources.empty(), "run_batch: no sources");
   for (int64_t v : sources) DBFS_CHECK(v >= 0 && v < part_.n, "run_batch: source vertex out of range");
   DBFS_CHECK(part_.nranks == 1 || dir != BatchDirection::Push,
@@ -273,10 +275,15 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirectio
   batch_parents_k_ = -1;
   batch_levels_.clear();
   batch_parents_.clear();
+  batch_dep_valid_ = false;
+  batch_counts_k_ = -1;
+  batch_counts_.clear();
+  if (keep_path_counts) batch_counts_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), 0.0);
   if (keep_levels) batch_levels_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), kUnreached);
   if (keep_parents) batch_parents_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.part), -1);
   if (validate) out.violations.assign(static_cast<size_t>(k) * kMsCheckCounters, 0);
   double ms = 0.0, check_ms = 0.0;
+  bool dep_zeroed = false;
   for (int pass = 0; pass < out.passes; ++pass) {
     const int64_t first = static_cast<int64_t>(pass) * kMsSources;
     const int kp = static_cast<int>(std::min<int64_t>(kMsSources, k - first));
@@ -319,9 +326,28 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirectio
                        keep_parents, first);
       check_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     }
+    if (betweenness || keep_path_counts) {
+      // (as the check: after the timed window, on the rerun's matrix when the
+      // pass was repeated, before the next pass reuses it; timed on its own)
+      if (betweenness && !dep_zeroed) {
+        if (ms_->bc_dep.size() == 0) ms_->bc_dep = DBuf<double>(be_, static_cast<size_t>(part_.part));
+        be_.memset_async(ms_->bc_dep.data(), 0, ms_->bc_dep.bytes());
+        dep_zeroed = true;
+      }
+      int depth = 0;
+      for (int t = 0; t < kp; ++t) depth = std::max(depth, out.depth[static_cast<size_t>(first + t)]);
+      bc_batch_pass(sources.data() + first, kp, depth, betweenness, keep_path_counts, first, out);
+    }
   }
   out.ms = comm_.max_host(ms);
   if (validate || keep_parents) out.check_ms = comm_.max_host(check_ms);
+  if (betweenness || keep_path_counts) {
+    out.bc_forward_ms = comm_.max_host(out.bc_forward_ms);
+    out.bc_backward_ms = comm_.max_host(out.bc_backward_ms);
+    out.bc_ms = comm_.max_host(out.bc_ms);
+  }
+  if (betweenness) batch_dep_valid_ = true;
+  if (keep_path_counts) batch_counts_k_ = k;
   if (keep_parents) batch_parents_k_ = k;
   int64_t edges = 0;
   for (int64_t e : out.edges) edges += e;
@@ -424,6 +450,151 @@ void Engine::check_batch_pass(const int64_t* src, int k, int64_t* viol, bool par
   }
   be_.synchronize();  // (a rank that copied nothing back: check_ms still ends with the work done)
   check_device();
+}
+
+// Backend::ms_bc_* on the pass's matrix: the sources' path counts level by
+// level outwards, then (accumulate) the dependencies from the deepest level
+// back, each level one launch.  Several ranks, the simple form: the level
+// matrix all-gathered as for the check, the value matrix replicated and the
+// owned lines all-gathered into it after every launch.  A directed graph's
+// forward sweep walks the in-edge shard, the backward one the out-edges.
+void Engine::bc_batch_pass(const int64_t* src, int k, int depth, bool accumulate, bool counts, int64_t first,
+                           BatchResult& out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int P = part_.nranks;
+  const int64_t W = part_.part, n = part_.n;
+  MsBuffers& b = *ms_;
+  DBFS_CHECK(b.lvl_bytes != 0, "batch betweenness: no level matrix is resident");
+  const size_t lvl_bytes = static_cast<size_t>(W) * kMsSources * b.lvl_bytes;
+  const size_t own_vals = static_cast<size_t>(W) * kMsSources;
+  DBuf<uint8_t> all;
+  if (P > 1) {
+    all = DBuf<uint8_t>(be_, lvl_bytes * P);
+    comm_.allgather(b.lvl.data(), all.data(), lvl_bytes);
+  }
+  if (b.bc_val.size() == 0) {
+    b.bc_val = DBuf<double>(be_, own_vals * P);
+    if (P > 1) b.bc_own = DBuf<double>(be_, own_vals);
+    b.bc_walked = DBuf<unsigned long long>(be_, 1);
+  }
+  be_.memset_async(b.bc_walked.data(), 0, b.bc_walked.bytes());
+  MsBcArgs a;
+  a.g = g_.view();
+  a.lvl = P > 1 ? all.data() : b.lvl.data();
+  a.lvl_bytes = b.lvl_bytes;
+  a.lvl_rows = W * P;
+  a.val = b.bc_val.data();
+  a.own = P > 1 ? b.bc_own.data() : b.bc_val.data();
+  a.dep = accumulate ? b.bc_dep.data() : nullptr;
+  a.k = k;
+  std::copy(src, src + k, a.src);
+  a.batch_mask = k == kMsSources ? ~word_t(0) : (word_t(1) << k) - 1;
+  a.walked = b.bc_walked.data();
+  // the long rows of a view, listed once per engine and threshold
+  auto long_rows = [&](int which, const ShardView& view) {
+    a.long_rows = nullptr;
+    a.n_long = 0;
+    a.split_above = opt_.bc_split_row;
+    if (opt_.bc_split_row <= 0) return;
+    if (b.bc_long_above != opt_.bc_split_row) {
+      b.bc_long_n[0] = b.bc_long_n[1] = -1;
+      b.bc_long_above = opt_.bc_split_row;
+    }
+    if (b.bc_long_n[which] < 0) {
+      const int64_t cap = view.nnz / opt_.bc_split_row + 1;
+      b.bc_long[which] = DBuf<vid_t>(be_, static_cast<size_t>(cap));
+      DBuf<unsigned long long> cnt(be_, 1);
+      be_.memset_async(cnt.data(), 0, cnt.bytes());
+      be_.ms_bc_long_rows(view.row_off, view.rows, opt_.bc_split_row, b.bc_long[which].data(), cap, cnt.data());
+      unsigned long long h = 0;
+      be_.to_host(&h, cnt.data(), sizeof(h));
+      DBFS_CHECK(static_cast<int64_t>(h) <= cap, "batch betweenness: more long rows than the shard can hold");
+      b.bc_long_n[which] = static_cast<int64_t>(h);
+    }
+    a.long_rows = b.bc_long[which].data();
+    a.n_long = b.bc_long_n[which];
+  };
+  auto share = [&] {  // (several ranks: every rank's new lines into every rank's matrix)
+    if (P > 1) comm_.allgather(b.bc_own.data(), b.bc_val.data(), own_vals * sizeof(double));
+  };
+  be_.ms_bc_init(a);
+  // forward: the predecessor rows
+  const ShardView pred = check_view();
+  a.row_off = pred.row_off;
+  a.col = pred.col;
+  a.nnz = pred.nnz;
+  long_rows(0, pred);
+  for (int level = 1; level < depth; ++level) {
+    a.level = level;
+    be_.ms_bc_forward(a);
+    share();
+    ++out.bc_launches;
+  }
+  if (fault_.kind == "bc_device" && fault_.rank == comm_.rank()) be_.inject_device_check();
+  if (counts) {
+    // vertex-major on the device, source-major on the host (as the parents)
+    constexpr int64_t kChunk = int64_t(1) << 14;
+    std::vector<double> hv(static_cast<size_t>(std::min(n, kChunk)) * kMsSources);
+    double* const base = batch_counts_.data() + static_cast<size_t>(first) * static_cast<size_t>(n);
+    for (int64_t v0 = 0; v0 < n; v0 += kChunk) {
+      const int64_t nv = std::min(kChunk, n - v0);
+      be_.to_host(hv.data(), b.bc_val.data() + static_cast<size_t>(v0) * kMsSources,
+                  static_cast<size_t>(nv) * kMsSources * sizeof(double));
+      for (int64_t v = 0; v < nv; ++v)
+        for (int t = 0; t < k; ++t)
+          base[static_cast<size_t>(t) * static_cast<size_t>(n) + static_cast<size_t>(v0 + v)] =
+              hv[static_cast<size_t>(v) * kMsSources + t];
+    }
+  }
+  be_.synchronize();
+  const auto t1 = std::chrono::steady_clock::now();
+  if (accumulate) {
+    // backward: the out-rows; level 0 holds the sources themselves, which
+    // take no share of their own dependencies
+    a.row_off = a.g.row_off;
+    a.col = a.g.col;
+    a.nnz = a.g.nnz;
+    long_rows(opt_.directed ? 1 : 0, a.g);
+    const int64_t n_long = a.n_long;
+    for (int level = depth - 1; level >= 1; --level) {
+      a.level = level;
+      a.leaf = level == depth - 1;
+      a.n_long = a.leaf ? 0 : n_long;  // (the deepest level walks no row: every vertex by its wave)
+      be_.ms_bc_backward(a);
+      share();
+      ++out.bc_launches;
+    }
+  }
+  unsigned long long walked = 0;
+  be_.to_host(&walked, b.bc_walked.data(), sizeof(walked));
+  out.bc_rows_walked += static_cast<int64_t>(walked);
+  be_.synchronize();
+  check_device();
+  const auto t2 = std::chrono::steady_clock::now();
+  out.bc_forward_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+  out.bc_backward_ms += std::chrono::duration<double, std::milli>(t2 - t1).count();
+  out.bc_ms += std::chrono::duration<double, std::milli>(t2 - t0).count();
+}
+
+std::vector<double> Engine::gather_betweenness() {
+  DBFS_CHECK(batch_dep_valid_ && ms_, "gather_betweenness: no batch has run with betweenness");
+  const int P = part_.nranks;
+  const int64_t W = part_.part, n = part_.n;
+  std::vector<double> h(static_cast<size_t>(W) * P);
+  if (P > 1) {
+    DBuf<double> allv(be_, h.size());
+    comm_.allgather(ms_->bc_dep.data(), allv.data(), static_cast<size_t>(W) * sizeof(double));
+    be_.to_host(h.data(), allv.data(), h.size() * sizeof(double));
+  } else {
+    be_.to_host(h.data(), ms_->bc_dep.data(), h.size() * sizeof(double));
+  }
+  h.resize(static_cast<size_t>(n));  // (slices are W vertices each: global vertex v is entry v)
+  return h;
+}
+
+std::vector<double> Engine::gather_batch_path_counts() {
+  DBFS_CHECK(batch_counts_k_ > 0, "gather_batch_path_counts: no batch has run with keep_path_counts");
+  return batch_counts_;
 }
 
 std::vector<int64_t> Engine::validate_batch_pass(const std::vector<int64_t>& sources) {

@@ -86,6 +86,7 @@ void set_engine_option(EngineOptions& o, const std::string& name, double v) {
   else if (name == "bu_cut_ranks") o.bu_cut_ranks = static_cast<int64_t>(v);
   else if (name == "list_cap_factor") o.list_cap_factor = v;
   else if (name == "direct_frontier") o.direct_frontier = v != 0;
+  else if (name == "bc_split_row") o.bc_split_row = static_cast<int64_t>(v);
   else throw Error("unknown engine option '" + name + "'");
 }
 
@@ -126,7 +127,8 @@ std::vector<std::pair<std::string, double>> engine_option_map(const EngineOption
           {"bu_cut_mf_frac", o.bu_cut_mf_frac},
           {"bu_cut_ranks", static_cast<double>(o.bu_cut_ranks)},
           {"list_cap_factor", o.list_cap_factor},
-          {"direct_frontier", o.direct_frontier ? 1.0 : 0.0}};
+          {"direct_frontier", o.direct_frontier ? 1.0 : 0.0},
+          {"bc_split_row", static_cast<double>(o.bc_split_row)}};
 }
 
 // ---- DeviceGraph ----------------------------------------------------------------
@@ -683,7 +685,9 @@ void Engine::read_level_stats(int64_t* host_stats) {
 // ranks abort their group), `exit` ends the process with status 17 (a crashed
 // rank), `hang` stops participating (peers must time out), `device` records
 // a device-check violation (the run fails when it ends), `batch_device` the
-// same at level L of a batch pass (run_batch fails after the pass),
+// same at level L of a batch pass (run_batch fails after the pass), `bc_device`
+// the same during a pass's dependency accumulation (run_batch(betweenness)
+// fails after it),
 // `in_edges_device` during DeviceGraph::build_in_edges, `delay` enqueues the
 // level ms late; kind=late_wg[,us=U] (every rank, every level) makes the
 // workgroups of a sparse top-down level that take no ticket start U us late
@@ -712,8 +716,8 @@ FaultSpec FaultSpec::from_env() {
   }
   DBFS_CHECK(f.kind == "throw" || f.kind == "exit" || f.kind == "hang" || f.kind == "device" || f.kind == "delay" ||
                  f.kind == "rccl_init" || f.kind == "peer_init" || f.kind == "late_wg" || f.kind == "batch_device" ||
-                 f.kind == "in_edges_device",
-             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|in_edges_device|delay|rccl_init|"
+                 f.kind == "in_edges_device" || f.kind == "bc_device",
+             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|bc_device|in_edges_device|delay|rccl_init|"
              "peer_init|late_wg");
   // (rccl_init / peer_init: the communicators' setup fails -- NcclComm /
   // PeerComm read them; late_wg: every sparse top-down level's ticket-less
@@ -744,7 +748,8 @@ void Engine::inject_batch_fault(int level) {
 }
 
 void Engine::inject_fault(int level) {
-  if (fault_.kind == "batch_device" || fault_.kind == "in_edges_device") return;  // (not a traversal's)
+  if (fault_.kind == "batch_device" || fault_.kind == "in_edges_device" || fault_.kind == "bc_device")
+    return;  // (not a traversal's)
   if (fault_.rank != comm_.rank() || fault_.level != level) return;
   if (fault_.kind == "device") {
     // a kernel-side bounds violation (recorded, not raised: the traversal

@@ -75,6 +75,62 @@ CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src) {
   return r;
 }
 
+CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t>& sources, bool directed,
+                                     bool want_counts) {
+  DBFS_CHECK(g.row_lo == 0 && g.rows == g.n, "cpu_betweenness expects a full CSR");
+  const size_t n = static_cast<size_t>(g.n);
+  CpuBetweennessResult r;
+  r.dep.assign(n, 0.0);
+  if (want_counts) r.sigma.assign(sources.size() * n, 0.0);
+  std::vector<lvl_t> dist(n);
+  std::vector<double> sigma(n), delta(n);
+  std::vector<vid_t> order;  // the queue; read backwards it is Brandes' stack
+  order.reserve(n);
+  for (size_t i = 0; i < sources.size(); ++i) {
+    const int64_t src = sources[i];
+    DBFS_CHECK(src >= 0 && src < g.n, "source vertex out of range");
+    std::fill(dist.begin(), dist.end(), kUnreached);
+    std::fill(sigma.begin(), sigma.end(), 0.0);
+    std::fill(delta.begin(), delta.end(), 0.0);
+    order.clear();
+    order.push_back(static_cast<vid_t>(src));
+    dist[src] = 0;
+    sigma[src] = 1.0;
+    for (size_t head = 0; head < order.size(); ++head) {
+      const vid_t u = order[head];
+      const lvl_t lu = dist[u];
+      if (!directed && lu > 0) {
+        // u's predecessors are in its own row, all dequeued before it
+        double s = 0.0;
+        for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e)
+          if (dist[g.col[e]] == lu - 1) s += sigma[g.col[e]];
+        sigma[u] = s;
+      }
+      for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e) {
+        const vid_t w = g.col[e];
+        if (dist[w] == kUnreached) {
+          dist[w] = lu + 1;
+          order.push_back(w);
+        }
+        // (u's count is final: every vertex one level closer was dequeued before it)
+        if (directed && dist[w] == lu + 1) sigma[w] += sigma[u];
+      }
+    }
+    for (size_t at = order.size(); at-- > 0;) {
+      const vid_t v = order[at];
+      double d = 0.0;
+      for (eid_t e = g.row_off[v]; e < g.row_off[v + 1]; ++e) {
+        const vid_t w = g.col[e];
+        if (dist[w] == dist[v] + 1) d += sigma[v] / sigma[w] * (1.0 + delta[w]);
+      }
+      delta[v] = d;
+      if (static_cast<int64_t>(v) != src) r.dep[v] += d;
+    }
+    if (want_counts) std::copy(sigma.begin(), sigma.end(), r.sigma.begin() + i * n);
+  }
+  return r;
+}
+
 int64_t traversed_edges(const HostCSR& g, const std::vector<lvl_t>& level) {
   int64_t s = 0;
   for (int64_t r = 0; r < g.rows; ++r)

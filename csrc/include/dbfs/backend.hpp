@@ -1147,6 +1147,60 @@ struct MsCheckArgs {
   bool directed = false;
 };
 
+// Shortest-path counts and Brandes dependencies of a finished pass, all its
+// sources at once (Engine::run_batch betweenness / keep_path_counts).  `lvl` is
+// the pass's full level matrix as in MsCheckArgs; `val` is a matrix of doubles
+// of the same shape (row v: the kMsSources values of global vertex v) and
+// `own` the lines of the owned rows, which a launch writes (one rank: val
+// itself; several: a buffer of its own, all-gathered into every rank's val
+// after each launch).  Entries are the stored adjacency entries, duplicates
+// and self-loops included; lvl_s is source s's column of the matrix.
+//   ms_bc_init      val[v][s] = own[..][s] = 1 for v == src[s], s < k; else 0.
+//   ms_bc_forward   level L: for every owned v and s with lvl_s(v) == L,
+//     own[v][s] = sum of val[u][s] over the entries u of v's row in
+//     (row_off, col) -- the predecessor rows: the in-edge shard of a directed
+//     graph, the shard's own rows otherwise -- with lvl_s(u) == L - 1, added in
+//     stored row order.  After levels 1 .. depth - 1 the matrix holds sigma.
+//   ms_bc_backward  level L, from the deepest down: for every owned v and s
+//     with lvl_s(v) == L, acc = sum of val[w][s] over the entries w of v's
+//     out-row (row_off, col = g's) with lvl_s(w) == L + 1 (leaf: the deepest
+//     level, nothing is walked and acc = 0); delta = sigma * acc with sigma =
+//     own[v][s], and own[v][s] becomes the coefficient (1 + delta) / sigma the
+//     level above adds up -- a lane reads only entries of the adjacent level,
+//     so counts and coefficients never mix.  dep[v] += the sum over the lanes
+//     s with v != src[s] of delta, reduced in a fixed order (lane i + lane
+//     i ^ 32, then ^ 16, ... ^ 1) and stored once per vertex: no atomics on
+//     floating-point values anywhere, results are deterministic.
+// No lane that is not at level L divides: an unreached vertex's 0 / 0 never
+// reaches memory.  walked (optional): += the rows the launch walked (those
+// with a lane at level L).
+struct MsBcArgs {
+  ShardView g;                      // the owned rows (lo, rows)
+  const eid_t* row_off = nullptr;   // the rows this launch walks (local offsets, global column ids)
+  const vid_t* col = nullptr;
+  int64_t nnz = 0;                  // entries of `col` (the checked build's bound)
+  const void* lvl = nullptr;
+  int lvl_bytes = 1;
+  int64_t lvl_rows = 0;             // rows of lvl and val (>= n)
+  double* val = nullptr;            // (written by ms_bc_init and the all-gathers only)
+  double* own = nullptr;            // g.rows x kMsSources
+  double* dep = nullptr;            // g.rows (backward)
+  int k = 0;
+  int64_t src[kMsSources] = {};     // global vertex ids
+  word_t batch_mask = 0;            // bit s set: s < k
+  int level = 0;
+  bool leaf = false;
+  unsigned long long* walked = nullptr;
+  // Long rows (HIP; optional): the n_long owned rows of more than split_above
+  // entries in (row_off, col), in any order (Backend::ms_bc_long_rows).  They
+  // are walked by a launch of their own, a workgroup of 16 waves per row, each
+  // wave a sixteenth of the row, the partial sums added in wave order -- not
+  // by the one wave the other rows get.  n_long = 0: every row by its wave.
+  const vid_t* long_rows = nullptr;
+  int64_t n_long = 0;
+  int64_t split_above = 0;
+};
+
 // ---- backend ----------------------------------------------------------------
 
 class Backend {
@@ -1361,6 +1415,14 @@ class Backend {
   virtual void ms_settle(const MsSettleArgs& a) = 0;
   virtual void ms_degree_sums(const MsDegreeArgs& a) = 0;
   virtual void ms_check(const MsCheckArgs& a) = 0;
+  // path counts and dependencies of a finished pass (MsBcArgs)
+  virtual void ms_bc_init(const MsBcArgs& a) = 0;
+  virtual void ms_bc_forward(const MsBcArgs& a) = 0;
+  virtual void ms_bc_backward(const MsBcArgs& a) = 0;
+  // list[0 .. *count) = the rows r < rows with row_off[r + 1] - row_off[r] >
+  // above, in some order (at most cap stored; *count zero on entry)
+  virtual void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
+                               unsigned long long* count) = 0;
 
  protected:
   std::function<void(double)> wait_watch_;

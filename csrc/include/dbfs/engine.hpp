@@ -389,6 +389,10 @@ struct EngineOptions {
   // trees build the graph's in-edge shard on their first call
   // (DeviceGraph::build_in_edges, or Engine::build_in_edges up front).
   bool directed = false;
+  // run_batch(betweenness / keep_path_counts): rows of more than this many
+  // entries are walked by a workgroup of 16 waves in a launch of their own
+  // (MsBcArgs::long_rows) instead of by one wave; 0: never.
+  int64_t bc_split_row = 512;
 };
 
 // Named access to the numeric tuning options (alpha, beta, bu_lane_limit,
@@ -487,6 +491,15 @@ struct BatchResult {
   // wall time of the per-pass checks (validate / keep_parents; max over
   // ranks): after each pass's timed window, never part of `ms`
   double check_ms = 0.0;
+  // run_batch(betweenness / keep_path_counts): wall time of the per-pass path
+  // counts and dependency accumulation (max over ranks), after each pass's
+  // timed window and its check: never part of `ms` or `check_ms`.  Its
+  // forward (init and path counts, the counts' copy included) and backward
+  // (dependencies) parts; the launches of all passes (one per level and
+  // direction) and the rows they walked on this rank (those with a source on
+  // the launch's level: launches x owned rows without that skip).
+  double bc_ms = 0.0, bc_forward_ms = 0.0, bc_backward_ms = 0.0;
+  int64_t bc_launches = 0, bc_rows_walked = 0;
 };
 
 // Fault injection for failure-detection tests (see Engine::inject_fault).
@@ -528,8 +541,28 @@ class Engine {
   // on the device during the check, k x 8 bytes per owned vertex on the host).
   // Both need keep_levels.  Several ranks: the owned slices of the matrix are
   // all-gathered for the check, as gather_batch_levels does.
+  // betweenness: after each pass (and its check) the shortest-path counts and
+  // Brandes' dependencies of its sources are computed on the device from the
+  // level matrix (Backend::ms_bc_*, one launch per level and direction) and
+  // summed into one vector for gather_betweenness (512 + 8 bytes per owned
+  // vertex on the device).  keep_path_counts: the same forward sweep also
+  // leaves every source's path counts for gather_batch_path_counts (k x n x 8
+  // bytes on the host).  Both need keep_levels; BatchResult::bc_ms.  Several
+  // ranks: the simple form -- the value matrix is replicated and the owned
+  // lines are all-gathered after every launch.
   BatchResult run_batch(const std::vector<int64_t>& sources, BatchDirection dir = BatchDirection::Auto,
-                        bool keep_levels = true, bool validate = false, bool keep_parents = false);
+                        bool keep_levels = true, bool validate = false, bool keep_parents = false,
+                        bool betweenness = false, bool keep_path_counts = false);
+  // The last batch's dependency sums, one per vertex: dep(v) = the sum over the
+  // source slots i with v != src_i of delta_{src_i}(v) -- raw: not halved on
+  // an undirected graph, not rescaled, not normalised; collective.  Throws
+  // when the batch ran without betweenness.
+  std::vector<double> gather_betweenness();
+  // The last batch's shortest-path counts, [k][n] row-major (0 where source k
+  // does not reach; exact while below 2^53).  Throws when the batch ran
+  // without keep_path_counts.
+  std::vector<double> gather_batch_path_counts();
+  int64_t batch_path_count_sources() const { return batch_counts_k_; }  // (-1: none)
   // The last batch's levels, [k][n] row-major, kUnreached where source k does
   // not reach; collective.  Throws when the batch ran without keep_levels.
   std::vector<lvl_t> gather_batch_levels();
@@ -683,6 +716,17 @@ class Engine {
     bool wide = false;  // a batch overflowed the one-byte levels: 16-bit from then on
     DBuf<int64_t> check;   // MsCheckArgs::out
     DBuf<uint32_t> par;    // MsCheckArgs::par (allocated by the first batch that keeps parents)
+    // MsBcArgs (allocated by the first batch that asks for betweenness or path
+    // counts): the value matrix, several ranks' owned lines, the dependency
+    // sums of the owned rows, the rows-walked counter
+    DBuf<double> bc_val, bc_own, bc_dep;
+    DBuf<unsigned long long> bc_walked;
+    // MsBcArgs::long_rows of the predecessor rows [0] and the out-rows [1]
+    // (an undirected graph: [0] for both), built on first use for
+    // EngineOptions::bc_split_row = bc_long_above (-1 entries: not built)
+    DBuf<vid_t> bc_long[2];
+    int64_t bc_long_n[2] = {-1, -1};
+    int64_t bc_long_above = 0;
   };
   std::unique_ptr<MsBuffers> ms_;
   // 0: done; 1: deeper than the level type holds (rerun wider)
@@ -700,6 +744,15 @@ class Engine {
   // batch_parents_ (parents set).  Blocking.
   void check_batch_pass(const int64_t* src, int k, int64_t* viol, bool parents, int64_t first);
   int batch_last_k_ = 0;                 // sources of the last pass whose level matrix is resident (0: none)
+  // Path counts and dependencies of the pass just run (sources src[0..k), the
+  // deepest of them `depth` levels): dependencies into MsBuffers::bc_dep
+  // (accumulate), path counts into rows [first, first + k) of batch_counts_
+  // (counts).  Blocking; the forward and backward times are added to `out`.
+  void bc_batch_pass(const int64_t* src, int k, int depth, bool accumulate, bool counts, int64_t first,
+                     BatchResult& out);
+  bool batch_dep_valid_ = false;         // the last batch accumulated dependencies
+  std::vector<double> batch_counts_;     // [k][n]
+  int64_t batch_counts_k_ = -1;          // sources of the last batch with path counts (-1: none)
   // owned slices of the parent trees, [k][part] (-1: unreached or padding)
   std::vector<int64_t> batch_parents_;
   int64_t batch_parents_k_ = -1;         // sources of the last batch with parents (-1: none)

@@ -90,6 +90,24 @@ struct CpuBfsResult {
 };
 CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src);
 
+// Sequential betweenness oracle (Brandes 2001: a queue, the visit order as a
+// stack, a predecessor scan), one source at a time.  Entries are the stored
+// adjacency entries, duplicates and self-loops kept: sigma_s(s) = 1, and for a
+// reached v != s sigma_s(v) = the sum of sigma_s(u) over the entries u -> v
+// with level(u) = level(v) - 1 (a duplicate counts again, a self-loop never);
+// delta_s(v) = the sum over the entries v -> w with level(w) = level(v) + 1 of
+// sigma_s(v) / sigma_s(w) (1 + delta_s(w)).  dep[v] = the sum over the source
+// slots i with v != sources[i] of delta_{sources[i]}(v): raw, not halved, not
+// rescaled.  directed: g holds out-entries only (the entries into v are found
+// from their tails' rows); otherwise g is symmetric and v's own row lists them.
+// sigma (want_counts): [k][n] row-major, 0 where unreached.
+struct CpuBetweennessResult {
+  std::vector<double> dep;
+  std::vector<double> sigma;
+};
+CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t>& sources, bool directed,
+                                     bool want_counts = false);
+
 // Traversed undirected edges (Graph500 convention): sum of degrees over
 // reached vertices / 2.
 int64_t traversed_edges(const HostCSR& g, const std::vector<lvl_t>& level);

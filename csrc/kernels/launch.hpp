@@ -68,6 +68,13 @@ void ms_settle(const MsSettleArgs& a, hipStream_t st);
 void ms_degree_sums(const MsDegreeArgs& a, hipStream_t st);
 void ms_check(const MsCheckArgs& a, hipStream_t st);
 
+// ms_bc_kernels.hip (path counts and dependencies of a finished batch pass)
+void ms_bc_init(const MsBcArgs& a, hipStream_t st);
+void ms_bc_forward(const MsBcArgs& a, hipStream_t st);
+void ms_bc_backward(const MsBcArgs& a, hipStream_t st);
+void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
+                     unsigned long long* count, hipStream_t st);
+
 // peer_kernels.hip (PeerComm: collectives through peer-mapped windows)
 constexpr int kMaxPeers = 16;
 struct PeerPushArgs {

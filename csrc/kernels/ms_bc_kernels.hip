@@ -1,0 +1,253 @@
+// Shortest-path counts and Brandes dependencies over a finished batch pass's
+// level matrix (gfx950, wave64; backend.hpp MsBcArgs).
+//
+//   ms_bc_init      the sources' 1.0 and the zeros
+//   ms_bc_forward   one level of path counts: sigma[v] = sum of sigma[u] over
+//                   v's predecessor entries one level closer
+//   ms_bc_backward  one level of dependencies, the matrix turned in place from
+//                   sigma into the coefficient (1 + delta) / sigma, and the
+//                   vertex's share of the centrality vector
+//
+// Both walks have ms_check_kernel's shape (ms_kernels.hip): a wave per owned
+// vertex, striding over the rows; lane s is source s; the row is read 64
+// column ids per step and for each of them lane s loads lvl[w][s], with
+// kMsBcAhead of those scattered lines requested before the first is consumed.
+// A value line (512 B per vertex) is touched only by the lanes whose level
+// matches, and a vertex none of whose lanes sits on the launch's level is
+// skipped after its own level line, before its row offsets are read.
+// Every sum is pull-form and per lane in stored row order: no atomics on
+// floating-point values, the same bits on every run.
+#include "kernel_common.hpp"
+
+namespace dbfs {
+namespace kern {
+namespace {
+
+constexpr int kMsBcBlock = 256;
+// Workgroups at most and lines in flight: ms_check_kernel's values (its
+// registers allow the same 8 waves per SIMD: profiles/ms_bfs_regs.txt).
+constexpr int kMsBcGrid = 2048;
+constexpr int kMsBcAhead = 8;
+
+// Sum over the wave in a fixed order (lane i + lane i ^ 32, then ^ 16 .. ^ 1;
+// every lane ends with the same bits).
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
+  return x;
+}
+
+__global__ __launch_bounds__(kMsBcBlock) void ms_bc_init_kernel(MsBcArgs a) {
+  const int lane = lane_id();
+  const int64_t my_src = ((a.batch_mask >> lane) & 1ull) ? a.src[lane] : -1;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + (threadIdx.x >> 6);
+  for (int64_t v = first; v < a.lvl_rows; v += stride) a.val[v * kMsSources + lane] = v == my_src ? 1.0 : 0.0;
+  for (int64_t r = first; r < a.g.rows; r += stride) a.own[r * kMsSources + lane] = a.g.lo + r == my_src ? 1.0 : 0.0;
+}
+
+// The sum, per lane, of val[w][lane] over the entries w of row [rs, re) whose
+// level is `want` -- for the lanes with `at` set; the others load no value.
+template <class L>
+__device__ __forceinline__ double ms_bc_row_sum(const MsBcArgs& a, const L* __restrict__ lvl, eid_t rs, eid_t re,
+                                                bool at, int want) {
+  constexpr int kNone = static_cast<int>(static_cast<L>(~static_cast<L>(0)));
+  const double* __restrict__ val = a.val;
+  const int lane = lane_id();
+  double sum = 0.0;
+  for (eid_t e = rs; e < re; e += kWave) {
+    const int cnt = static_cast<int>(min(static_cast<eid_t>(kWave), re - e));
+    const vid_t mine = lane < cnt ? a.col[e + lane] : 0u;
+    DBFS_DCHECK(static_cast<int64_t>(mine) < a.lvl_rows, 28, mine);
+    for (int j = 0; j < cnt; j += kMsBcAhead) {
+      int64_t at_w[kMsBcAhead];
+      int lw[kMsBcAhead];
+      double x[kMsBcAhead];
+#pragma unroll
+      for (int i = 0; i < kMsBcAhead; ++i) {
+        // (the last group of a row repeats its last entry's line instead of branching around the loads)
+        const vid_t w = static_cast<vid_t>(__builtin_amdgcn_readlane(static_cast<int>(mine), min(j + i, cnt - 1)));
+        at_w[i] = static_cast<int64_t>(w) * kMsSources + lane;
+        lw[i] = lvl[at_w[i]];
+      }
+#pragma unroll
+      for (int i = 0; i < kMsBcAhead; ++i) {
+        const bool valid = j + i < cnt;  // (wave-uniform)
+        x[i] = valid && at && lw[i] == want && lw[i] != kNone ? val[at_w[i]] : 0.0;
+      }
+#pragma unroll
+      for (int i = 0; i < kMsBcAhead; ++i) sum += x[i];  // (stored row order; + 0.0 changes no bit of a sum >= 0)
+    }
+  }
+  return sum;
+}
+
+// A vertex's forward result: the path counts of the lanes on the level.
+__device__ __forceinline__ void ms_bc_store_forward(const MsBcArgs& a, int64_t r, bool at, double sum) {
+  if (at) a.own[r * kMsSources + lane_id()] = sum;
+}
+
+// A vertex's backward result from acc, the sum of its successors'
+// coefficients: delta, the vertex's own coefficient in place of sigma, and
+// its share of dep.  Wave-uniform call.
+__device__ __forceinline__ void ms_bc_store_backward(const MsBcArgs& a, int64_t r, bool at, bool counts, double acc) {
+  const int lane = lane_id();
+  double delta = 0.0;
+  if (at) {  // (reached: sigma >= 1; no other lane divides)
+    const double sigma = a.own[r * kMsSources + lane];
+    delta = sigma * acc;
+    a.own[r * kMsSources + lane] = (1.0 + delta) / sigma;
+  }
+  if (__ballot(counts) == 0ull) return;
+  const double mine = wave_sum_f64(counts ? delta : 0.0);
+  if (lane == 0) a.dep[r] += mine;  // (one wave per vertex and launch: a plain store)
+}
+
+template <class L>
+__global__ __launch_bounds__(kMsBcBlock) void ms_bc_forward_kernel(MsBcArgs a) {
+  const ShardView& g = a.g;
+  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
+  const int lane = lane_id();
+  const bool on = (a.batch_mask >> lane) & 1ull;  // lanes past the pass's sources are idle
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  unsigned long long walked = 0;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
+  for (int64_t r = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + wave; r < g.rows; r += stride) {
+    const int64_t v = g.lo + r;
+    DBFS_DCHECK(v < a.lvl_rows, 27, v);
+    const bool at = on && static_cast<int>(lvl[v * kMsSources + lane]) == a.level;
+    if (__ballot(at) == 0ull) continue;
+    const eid_t rs = a.row_off[r], re = a.row_off[r + 1];
+    DBFS_DCHECK(rs >= 0 && rs <= re && re <= a.nnz, 29, r);
+    if (a.n_long > 0 && re - rs > a.split_above) continue;  // (ms_bc_long_kernel's)
+    ++walked;
+    ms_bc_store_forward(a, r, at, ms_bc_row_sum<L>(a, lvl, rs, re, at, a.level - 1));
+  }
+  if (a.walked && lane == 0 && walked) atomicAdd(a.walked, walked);
+}
+
+template <class L>
+__global__ __launch_bounds__(kMsBcBlock) void ms_bc_backward_kernel(MsBcArgs a) {
+  const ShardView& g = a.g;
+  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
+  const int lane = lane_id();
+  const bool on = (a.batch_mask >> lane) & 1ull;
+  const int64_t my_src = on ? a.src[lane] : -1;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  unsigned long long walked = 0;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
+  for (int64_t r = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + wave; r < g.rows; r += stride) {
+    const int64_t v = g.lo + r;
+    DBFS_DCHECK(v < a.lvl_rows, 27, v);
+    const bool at = on && static_cast<int>(lvl[v * kMsSources + lane]) == a.level;
+    if (__ballot(at) == 0ull) continue;
+    double acc = 0.0;
+    if (!a.leaf) {
+      const eid_t rs = a.row_off[r], re = a.row_off[r + 1];
+      DBFS_DCHECK(rs >= 0 && rs <= re && re <= a.nnz, 29, r);
+      if (a.n_long > 0 && re - rs > a.split_above) continue;  // (ms_bc_long_kernel's)
+      acc = ms_bc_row_sum<L>(a, lvl, rs, re, at, a.level + 1);
+    }
+    ++walked;
+    ms_bc_store_backward(a, r, at, at && v != my_src, acc);
+  }
+  if (a.walked && lane == 0 && walked) atomicAdd(a.walked, walked);
+}
+
+// The rows of more than split_above entries (MsBcArgs::long_rows), a
+// workgroup of 16 waves per row: wave w walks the w-th sixteenth of the row
+// (whole 64-entry steps), the partial sums meet in LDS and wave 0 adds them in
+// wave order, then finishes the vertex as the kernels above do -- a hub's row
+// is 1/16 of one wave's walk, and the result is the same on every run.
+constexpr int kMsBcLongBlock = 1024;
+constexpr int kMsBcLongWaves = kMsBcLongBlock / kWave;
+
+template <class L, bool kBackward>
+__global__ __launch_bounds__(kMsBcLongBlock) void ms_bc_long_kernel(MsBcArgs a) {
+  __shared__ double s_part[kMsBcLongWaves][kWave];
+  const ShardView& g = a.g;
+  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
+  const int lane = lane_id();
+  const bool on = (a.batch_mask >> lane) & 1ull;
+  const int64_t my_src = on ? a.src[lane] : -1;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  unsigned long long walked = 0;
+  for (int64_t i = blockIdx.x; i < a.n_long; i += gridDim.x) {
+    const int64_t r = a.long_rows[i];
+    const int64_t v = g.lo + r;
+    DBFS_DCHECK(r < g.rows && v < a.lvl_rows, 30, r);
+    // (every wave reads the same line: the skip is uniform over the workgroup)
+    const bool at = on && static_cast<int>(lvl[v * kMsSources + lane]) == a.level;
+    if (__ballot(at) == 0ull) continue;
+    const eid_t rs = a.row_off[r], re = a.row_off[r + 1];
+    DBFS_DCHECK(rs >= 0 && rs <= re && re <= a.nnz, 29, r);
+    const eid_t chunk = (((re - rs + kMsBcLongWaves - 1) / kMsBcLongWaves) + kWave - 1) & ~static_cast<eid_t>(kWave - 1);
+    const eid_t b = min(re, rs + wave * chunk), en = min(re, b + chunk);
+    s_part[wave][lane] = ms_bc_row_sum<L>(a, lvl, b, en, at, kBackward ? a.level + 1 : a.level - 1);
+    __syncthreads();
+    if (wave == 0) {
+      double sum = 0.0;
+#pragma unroll
+      for (int w = 0; w < kMsBcLongWaves; ++w) sum += s_part[w][lane];
+      ++walked;
+      if (kBackward) ms_bc_store_backward(a, r, at, at && v != my_src, sum);
+      else ms_bc_store_forward(a, r, at, sum);
+    }
+    __syncthreads();  // (s_part is the next row's)
+  }
+  if (a.walked && threadIdx.x == 0 && walked) atomicAdd(a.walked, walked);
+}
+
+__global__ __launch_bounds__(kMsBcBlock) void ms_bc_long_rows_kernel(const eid_t* row_off, int64_t rows, int64_t above,
+                                                                      vid_t* list, int64_t cap,
+                                                                      unsigned long long* count) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kMsBcBlock;
+  for (int64_t r = static_cast<int64_t>(blockIdx.x) * kMsBcBlock + threadIdx.x; r < rows; r += stride) {
+    if (row_off[r + 1] - row_off[r] <= above) continue;
+    const unsigned long long at = atomicAdd(count, 1ull);
+    if (at < static_cast<unsigned long long>(cap)) list[at] = static_cast<vid_t>(r);
+  }
+}
+
+template <class L, bool kBackward>
+void ms_bc_long_launch(const MsBcArgs& a, hipStream_t st) {
+  if (a.n_long <= 0) return;
+  ms_bc_long_kernel<L, kBackward><<<grid_for(a.n_long, 1, kMsBcGrid), kMsBcLongBlock, 0, st>>>(a);
+}
+
+}  // namespace
+
+void ms_bc_init(const MsBcArgs& a, hipStream_t st) {
+  if (a.lvl_rows <= 0) return;
+  ms_bc_init_kernel<<<grid_for(a.lvl_rows, kMsBcBlock / kWave, kMsBcGrid), kMsBcBlock, 0, st>>>(a);
+}
+
+void ms_bc_forward(const MsBcArgs& a, hipStream_t st) {
+  if (a.g.rows <= 0) return;
+  const unsigned grid = grid_for(a.g.rows, kMsBcBlock / kWave, kMsBcGrid);
+  if (a.lvl_bytes == 2) ms_bc_forward_kernel<uint16_t><<<grid, kMsBcBlock, 0, st>>>(a);
+  else ms_bc_forward_kernel<uint8_t><<<grid, kMsBcBlock, 0, st>>>(a);
+  if (a.lvl_bytes == 2) ms_bc_long_launch<uint16_t, false>(a, st);
+  else ms_bc_long_launch<uint8_t, false>(a, st);
+}
+
+void ms_bc_backward(const MsBcArgs& a, hipStream_t st) {
+  if (a.g.rows <= 0) return;
+  const unsigned grid = grid_for(a.g.rows, kMsBcBlock / kWave, kMsBcGrid);
+  if (a.lvl_bytes == 2) ms_bc_backward_kernel<uint16_t><<<grid, kMsBcBlock, 0, st>>>(a);
+  else ms_bc_backward_kernel<uint8_t><<<grid, kMsBcBlock, 0, st>>>(a);
+  if (a.lvl_bytes == 2) ms_bc_long_launch<uint16_t, true>(a, st);
+  else ms_bc_long_launch<uint8_t, true>(a, st);
+}
+
+void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
+                     unsigned long long* count, hipStream_t st) {
+  if (rows <= 0) return;
+  ms_bc_long_rows_kernel<<<grid_for(rows, kMsBcBlock, kMsBcGrid), kMsBcBlock, 0, st>>>(row_off, rows, above, list, cap,
+                                                                                      count);
+}
+
+unsigned long long take_check_ms_bc() { return take_check_local(); }
+
+}  // namespace kern
+}  // namespace dbfs

@@ -194,6 +194,21 @@ PYBIND11_MODULE(_dbfs_native, m) {
   m.def("write_levels", [](const std::string& path, py::array_t<int32_t, py::array::c_style | py::array::forcecast> l) {
     write_levels(path, from_numpy<int32_t>(l));
   });
+  // sequential Brandes oracle: (dep float64 [n], path counts float64 [k, n] or None)
+  m.def(
+      "cpu_betweenness",
+      [](const HostCSR& g, const std::vector<int64_t>& sources, bool directed, bool path_counts) -> py::tuple {
+        CpuBetweennessResult r;
+        {
+          py::gil_scoped_release rel;
+          r = cpu_betweenness(g, sources, directed, path_counts);
+        }
+        if (!path_counts) return py::make_tuple(to_numpy(r.dep), py::none());
+        py::array_t<double> sg = to_numpy(r.sigma);
+        sg.resize({static_cast<py::ssize_t>(sources.size()), static_cast<py::ssize_t>(g.n)});
+        return py::make_tuple(to_numpy(r.dep), sg);
+      },
+      py::arg("csr"), py::arg("sources"), py::arg("directed") = false, py::arg("path_counts") = false);
   m.def(
       "cpu_bfs",
       [](const HostCSR& g, int64_t src) {
@@ -707,6 +722,11 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def_readonly("dist_sum", &BatchResult::dist_sum)
       .def_readonly("discovered", &BatchResult::discovered)
       .def_readonly("check_ms", &BatchResult::check_ms)
+      .def_readonly("bc_ms", &BatchResult::bc_ms)
+      .def_readonly("bc_forward_ms", &BatchResult::bc_forward_ms)
+      .def_readonly("bc_backward_ms", &BatchResult::bc_backward_ms)
+      .def_readonly("bc_launches", &BatchResult::bc_launches)
+      .def_readonly("bc_rows_walked", &BatchResult::bc_rows_walked)
       // run_batch(validate=True): per source (gap, cross, orphan); else empty
       .def_property_readonly("violations",
                              [](const BatchResult& r) {
@@ -773,17 +793,41 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def(
           "run_batch",
           [](Engine& e, const std::vector<int64_t>& sources, const std::string& direction, bool levels, bool validate,
-             bool parents) {
+             bool parents, bool betweenness, bool path_counts) {
             const BatchDirection d = parse_batch_direction(direction);
             BatchResult r;
             {
               py::gil_scoped_release rel;
-              r = e.run_batch(sources, d, levels, validate, parents);
+              r = e.run_batch(sources, d, levels, validate, parents, betweenness, path_counts);
             }
             return r;
           },
           py::arg("sources"), py::arg("direction") = "auto", py::arg("levels") = true, py::arg("validate") = false,
-          py::arg("parents") = false)
+          py::arg("parents") = false, py::arg("betweenness") = false, py::arg("path_counts") = false)
+      // the last batch's raw dependency sums: float64 [n]
+      .def("gather_betweenness",
+           [](Engine& e) {
+             std::vector<double> v;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_betweenness();
+             }
+             return to_numpy(v);
+           })
+      // the last batch's shortest-path counts: float64 [k, n]
+      .def("gather_batch_path_counts",
+           [](Engine& e) {
+             std::vector<double> v;
+             int64_t k = 0;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_batch_path_counts();
+               k = e.batch_path_count_sources();
+             }
+             py::array_t<double> a = to_numpy(v);
+             a.resize({static_cast<py::ssize_t>(k), static_cast<py::ssize_t>(k ? v.size() / k : 0)});
+             return a;
+           })
       .def("build_in_edges", &Engine::build_in_edges, py::call_guard<py::gil_scoped_release>())
       .def("gather_batch_parents",
            [](Engine& e) {

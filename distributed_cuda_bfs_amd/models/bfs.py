@@ -84,15 +84,25 @@ class BatchResult:
     in-neighbour one level closer (``utils.validate.directed_levels_violations``)
     -- and ``validated``, True when every count is zero; both None when the check was
     not asked for.  ``check_ms``: wall time of the per-pass checks (validation
-    and parents), which ``ms`` never includes; 0.0 without them."""
+    and parents), which ``ms`` never includes; 0.0 without them.
+
+    With ``run_batch(betweenness=True)`` or ``path_counts=True``: ``bc_ms``,
+    the wall time of the per-pass path counts and dependency accumulation
+    (never part of ``ms`` or ``check_ms``), its ``bc_forward_ms`` /
+    ``bc_backward_ms`` parts, ``bc_launches`` (one per level and direction)
+    and ``bc_rows_walked`` (the rows those launches walked on this rank: the
+    ones with a source on the launch's level); zeros without them."""
 
     __slots__ = ("sources", "ms", "gteps", "passes", "wide_levels", "reached", "edges", "depth", "dist_sum",
-                 "discovered", "levels", "violations", "validated", "check_ms")
+                 "discovered", "levels", "violations", "validated", "check_ms", "bc_ms", "bc_forward_ms",
+                 "bc_backward_ms", "bc_launches", "bc_rows_walked")
 
     def __init__(self, r: Any, validate: bool = False):
         self.violations = [tuple(int(x) for x in v) for v in r.violations] if validate else None
         self.validated = all(v == (0, 0, 0) for v in self.violations) if validate else None
         self.check_ms = float(r.check_ms)
+        self.bc_ms, self.bc_forward_ms, self.bc_backward_ms = float(r.bc_ms), float(r.bc_forward_ms), float(r.bc_backward_ms)
+        self.bc_launches, self.bc_rows_walked = int(r.bc_launches), int(r.bc_rows_walked)
         self.sources, self.ms, self.gteps, self.passes = list(r.sources), r.ms, r.gteps, r.passes
         self.wide_levels = bool(r.wide_levels)
         self.reached, self.edges, self.depth = list(r.reached), list(r.edges), list(r.depth)
@@ -201,7 +211,7 @@ class BFS:
         return [BFSResult.from_native(r) for r in self.engine.run_many([int(s) for s in sources])]
 
     def run_batch(self, sources, direction: str = "auto", levels: bool = True, validate: bool = False,
-                  parents: bool = False) -> BatchResult:
+                  parents: bool = False, betweenness: bool = False, path_counts: bool = False) -> BatchResult:
         """One concurrent traversal from all ``sources`` (64 per pass, one bit
         per source in a 64-bit word per vertex); collective like run().
         ``direction``: "auto" picks push or pull per level (one rank; several
@@ -218,13 +228,42 @@ class BFS:
         ``validated``.  ``parents=True`` also keeps every source's parent tree
         for batch_parents().  Both read the level matrix (``levels=True``) and
         run after each pass's timed window: ``BatchResult.check_ms``, never
-        ``ms``."""
+        ``ms``.
+
+        ``betweenness=True`` computes, after each pass, the number of shortest
+        paths from each of its sources and Brandes' dependencies on the device
+        (one launch per level outwards and one per level back, over the level
+        matrix) and sums them over all sources for batch_betweenness().
+        ``path_counts=True`` keeps the path counts for batch_path_counts().
+        Both read the level matrix (``levels=True``) and are timed on their
+        own: ``BatchResult.bc_ms``.  512 + 8 bytes per owned vertex on the
+        device.  Several ranks use a simple replicated form: correct, not fast."""
         if direction not in BATCH_DIRECTIONS:
             raise ValueError(f"direction must be one of {BATCH_DIRECTIONS}")
         if (validate or parents) and not levels:
             raise ValueError("validate and parents read the level matrix: levels=True")
+        if (betweenness or path_counts) and not levels:
+            raise ValueError("betweenness and path_counts read the level matrix (keep_levels): levels=True")
         return BatchResult(self.engine.run_batch([int(s) for s in sources], direction, bool(levels), bool(validate),
-                                                 bool(parents)), validate=bool(validate))
+                                                 bool(parents), bool(betweenness), bool(path_counts)),
+                           validate=bool(validate))
+
+    def batch_betweenness(self) -> np.ndarray:
+        """Dependency sums of the last run_batch(betweenness=True) as float64 [n]:
+        dep[v] = the sum, over the source slots i with v != sources[i], of
+        Brandes' dependency of sources[i] on v, where parallel (duplicate)
+        entries are distinct paths and a source listed twice counts twice.
+        Raw: not halved on an undirected graph, not rescaled for sampled
+        sources, not normalised -- ``utils.centrality.betweenness_scores`` does
+        that.  Collective; raises when the last batch did not ask for it."""
+        return self.engine.gather_betweenness()
+
+    def batch_path_counts(self) -> np.ndarray:
+        """Shortest-path counts of the last run_batch(path_counts=True) as
+        float64 [k, n]: row i holds the number of shortest paths from
+        sources[i] to every vertex (1 for the source itself, 0 where it does
+        not reach), exact while below 2**53.  k x n x 8 bytes on the host."""
+        return self.engine.gather_batch_path_counts()
 
     def batch_levels(self) -> np.ndarray:
         """Levels of the last run_batch as int32 [k, n] (UNREACHED where a
