@@ -195,8 +195,9 @@ class CpuBackend final : public Backend {
   }
   // ---- concurrent multi-source BFS (backend.hpp MsState): plain loops ----
   static void ms_store_level(const MsState& s, int64_t row, int src, int level) {
-    if (s.lvl_bytes == 2) static_cast<uint16_t*>(s.lvl)[row * kMsSources + src] = static_cast<uint16_t>(level);
-    else static_cast<uint8_t*>(s.lvl)[row * kMsSources + src] = static_cast<uint8_t>(level);
+    ms_level_type(s.lvl_bytes, [&](auto l) {
+      static_cast<decltype(l)*>(s.lvl)[row * kMsSources + src] = static_cast<decltype(l)>(level);
+    });
   }
   static void ms_publish(const MsState& s) {
     if (!s.mailbox) return;
@@ -305,21 +306,17 @@ class CpuBackend final : public Backend {
   }
   void ms_check(const MsCheckArgs& a) override {
     const ShardView& g = a.g;
-    const int none = a.lvl_bytes == 2 ? kMsUnreached16 : kMsUnreached8;
-    auto level = [&](int64_t v, int s) -> int {
-      const int64_t i = v * kMsSources + s;
-      return a.lvl_bytes == 2 ? static_cast<const uint16_t*>(a.lvl)[i] : static_cast<const uint8_t*>(a.lvl)[i];
-    };
+    const int none = ms_unreached(a.m.lvl_bytes);
     for (int64_t r = 0; r < g.rows; ++r) {
       const int64_t u = g.lo + r;
-      for (int s = 0; s < a.k; ++s) {
-        const int lu = level(u, s);
+      for (int s = 0; s < a.m.k; ++s) {
+        const int lu = level_at(a.m, u, s);
         int64_t gap = 0, cross = 0;
         uint32_t par = kMsNoParent;
         bool has_parent = false;
         for (eid_t e = g.row_off[r]; e < g.row_off[r + 1]; ++e) {
           const vid_t w = g.col[e];
-          const int lw = level(w, s);
+          const int lw = level_at(a.m, w, s);
           if (a.directed) {
             // (in-edge row of u: the entry is w -> u)
             if (lw == none) continue;
@@ -335,7 +332,7 @@ class CpuBackend final : public Backend {
             par = w;
           }
         }
-        const bool is_src = u == a.src[s];
+        const bool is_src = u == a.m.src[s];
         if (a.out) {
           a.out[kMsCheckCounters * s + 0] += gap;
           a.out[kMsCheckCounters * s + 1] += cross;
@@ -347,24 +344,19 @@ class CpuBackend final : public Backend {
   }
   // ---- path counts and dependencies (backend.hpp MsBcArgs): plain loops, every
   // sum in the kernels' order (stored row order per source, the lanes' tree) ----
-  static int bc_level(const MsBcArgs& a, int64_t v, int s) {
-    const int64_t i = v * kMsSources + s;
-    return a.lvl_bytes == 2 ? static_cast<const uint16_t*>(a.lvl)[i] : static_cast<const uint8_t*>(a.lvl)[i];
-  }
   static double bc_row_sum(const MsBcArgs& a, int64_t r, int s, int want) {
-    const int none = a.lvl_bytes == 2 ? kMsUnreached16 : kMsUnreached8;
     double sum = 0.0;
-    if (want == none) return sum;
+    if (want == ms_unreached(a.m.lvl_bytes)) return sum;
     for (eid_t e = a.row_off[r]; e < a.row_off[r + 1]; ++e) {
       const vid_t w = a.col[e];
-      if (bc_level(a, w, s) == want) sum += a.val[static_cast<int64_t>(w) * kMsSources + s];
+      if (level_at(a.m, w, s) == want) sum += a.val[static_cast<int64_t>(w) * kMsSources + s];
     }
     return sum;
   }
   void ms_bc_init(const MsBcArgs& a) override {
     for (int s = 0; s < kMsSources; ++s) {
-      const int64_t src = s < a.k ? a.src[s] : -1;
-      for (int64_t v = 0; v < a.lvl_rows; ++v) a.val[v * kMsSources + s] = v == src ? 1.0 : 0.0;
+      const int64_t src = s < a.m.k ? a.m.src[s] : -1;
+      for (int64_t v = 0; v < a.m.lvl_rows; ++v) a.val[v * kMsSources + s] = v == src ? 1.0 : 0.0;
       for (int64_t r = 0; r < a.g.rows; ++r) a.own[r * kMsSources + s] = a.g.lo + r == src ? 1.0 : 0.0;
     }
   }
@@ -380,8 +372,8 @@ class CpuBackend final : public Backend {
   void ms_bc_forward(const MsBcArgs& a) override {
     for (int64_t r = 0; r < a.g.rows; ++r) {
       bool any = false;
-      for (int s = 0; s < a.k; ++s) {
-        if (bc_level(a, a.g.lo + r, s) != a.level) continue;
+      for (int s = 0; s < a.m.k; ++s) {
+        if (level_at(a.m, a.g.lo + r, s) != a.level) continue;
         any = true;
         a.own[r * kMsSources + s] = bc_row_sum(a, r, s, a.level - 1);
       }
@@ -393,14 +385,14 @@ class CpuBackend final : public Backend {
       const int64_t v = a.g.lo + r;
       double lane[kMsSources] = {};
       bool any = false, counts = false;
-      for (int s = 0; s < a.k; ++s) {
-        if (bc_level(a, v, s) != a.level) continue;
+      for (int s = 0; s < a.m.k; ++s) {
+        if (level_at(a.m, v, s) != a.level) continue;
         any = true;
         const double acc = a.leaf ? 0.0 : bc_row_sum(a, r, s, a.level + 1);
         const double sigma = a.own[r * kMsSources + s];
         const double delta = sigma * acc;
         a.own[r * kMsSources + s] = (1.0 + delta) / sigma;
-        if (v != a.src[s]) {
+        if (v != a.m.src[s]) {
           lane[s] = delta;
           counts = true;
         }

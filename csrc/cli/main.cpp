@@ -608,15 +608,18 @@ int main(int argc, char** argv) {
       // ---- the K roots as one concurrent traversal ----
       const std::vector<int64_t> roots = sample_roots(a, part, ranks, multiproc, wrank);
       const bool check = a.oracle && have_host;  // (the same on every rank of this process)
-      const BatchDirection bdir = parse_batch_direction(a.batch_dir);
+      BatchOptions bopt;
+      bopt.direction = parse_batch_direction(a.batch_dir);
+      // (--validate, --betweenness: they read the level matrix, oracle or not)
+      bopt.keep_levels = a.oracle || a.validate || a.betweenness;
+      bopt.validate = a.validate;
+      bopt.betweenness = a.betweenness;
       std::vector<BatchResult> bres(static_cast<size_t>(nlocal));
       std::vector<lvl_t> blv;
       std::vector<double> bdep;
       if (!roots.empty())
         run_ranks(ranks, [&](int i, RankCtx& rc) {
-          // (--validate, --betweenness: they read the level matrix, oracle or not)
-          bres[i] = rc.engine->run_batch(roots, bdir, a.oracle || a.validate || a.betweenness, a.validate, false,
-                                         a.betweenness, false);
+          bres[i] = rc.engine->run_batch(roots, bopt);
           if (a.betweenness) {
             std::vector<double> d = rc.engine->gather_betweenness();
             if (i == 0) bdep = std::move(d);

@@ -37,8 +37,27 @@ namespace {
 constexpr int64_t kMsPullEnter = 8;
 constexpr int64_t kMsPushBack = 64;
 
-// Deepest level a level matrix entry holds (its all-ones value reads unreached).
-constexpr int kMsMaxLevel8 = kMsUnreached8 - 1, kMsMaxLevel16 = kMsUnreached16 - 1;
+// Vertex-major on the device, source-major on the host: the device matrix
+// dev[rows][kMsSources] into the host rows host[t * stride + r], t < k, each
+// entry through conv, copied and transposed kMsCopyRows rows at a time (a host
+// temporary of 4 MB for one-byte levels, 32 MB for path counts).
+constexpr int64_t kMsCopyRows = int64_t(1) << 16;
+template <class TDev, class THost, class Conv>
+void copy_transposed(Backend& be, const TDev* dev, int64_t rows, int k, THost* host, size_t stride, Conv conv) {
+  std::vector<TDev> h(static_cast<size_t>(std::min(rows, kMsCopyRows)) * kMsSources);
+  for (int64_t r0 = 0; r0 < rows; r0 += kMsCopyRows) {
+    const int64_t nr = std::min(kMsCopyRows, rows - r0);
+    be.to_host(h.data(), dev + static_cast<size_t>(r0) * kMsSources, static_cast<size_t>(nr) * kMsSources * sizeof(TDev));
+    for (int64_t r = 0; r < nr; ++r) {
+      const TDev* line = h.data() + static_cast<size_t>(r) * kMsSources;
+      for (int t = 0; t < k; ++t) host[static_cast<size_t>(t) * stride + static_cast<size_t>(r0 + r)] = conv(line[t]);
+    }
+  }
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 }  // namespace
 
@@ -87,7 +106,8 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
       b.lvl_bytes = lvl_bytes;
     }
   }
-  const int max_level = lvl_bytes == 1 ? kMsMaxLevel8 : kMsMaxLevel16;
+  // the deepest level an entry holds (without a matrix: as deep as 16-bit ones would)
+  const int max_level = ms_unreached(lvl_bytes ? lvl_bytes : 2) - 1;
 
   MsState s;
   s.g = g_.view();
@@ -104,7 +124,7 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
   s.next = b.next.data();
   s.lvl = lvl_bytes ? b.lvl.data() : nullptr;
   s.lvl_bytes = lvl_bytes;
-  s.batch_mask = k == kMsSources ? ~word_t(0) : (word_t(1) << k) - 1;
+  s.batch_mask = ms_batch_mask(k);
   s.cursor = b.cursor.data();
   s.tot = b.tot.data();
   s.ticket = b.ticket.data();
@@ -254,43 +274,32 @@ int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection d
   return 0;
 }
 
-BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirection dir, bool keep_levels, bool validate,
-                              bool keep_parents, bool betweenness, bool keep_path_counts) {
-  DBFS_CHECK(keep_levels || !(validate || keep_parents),
-             "run_batch: validate and keep_parents read the level matrix (keep_levels)");
-  DBFS_CHECK(keep_levels || !(betweenness || keep_path_counts),
+BatchResult Engine::run_batch(const std::vector<int64_t>& sources, const BatchOptions& o) {
+  const bool check = o.validate || o.keep_parents, bc = o.betweenness || o.keep_path_counts;
+  DBFS_CHECK(o.keep_levels || !check, "run_batch: validate and keep_parents read the level matrix (keep_levels)");
+  DBFS_CHECK(o.keep_levels || !bc,
              "run_batch: betweenness and keep_path_counts read the level matrix (keep_levels)");
   DBFS_CHECK(!sources.empty(), "run_batch: no sources");
   for (int64_t v : sources) DBFS_CHECK(v >= 0 && v < part_.n, "run_batch: source vertex out of range");
-  DBFS_CHECK(part_.nranks == 1 || dir != BatchDirection::Push,
+  DBFS_CHECK(part_.nranks == 1 || o.direction != BatchDirection::Push,
              "run_batch: the push form runs on one rank only (several ranks: every level is a pull)");
   build_in_edges();  // (a directed graph's first batch; outside the timed window)
   const int64_t k = static_cast<int64_t>(sources.size());
   BatchResult out;
   out.sources = sources;
   out.passes = static_cast<int>(div_up(k, kMsSources));
-  batch_k_ = -1;
-  batch_pending_first_ = -1;
-  batch_last_k_ = 0;
-  batch_parents_k_ = -1;
-  batch_levels_.clear();
-  batch_parents_.clear();
-  batch_dep_valid_ = false;
-  batch_counts_k_ = -1;
-  batch_counts_.clear();
-  if (keep_path_counts) batch_counts_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), 0.0);
-  if (keep_levels) batch_levels_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), kUnreached);
-  if (keep_parents) batch_parents_.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.part), -1);
-  if (validate) out.violations.assign(static_cast<size_t>(k) * kMsCheckCounters, 0);
+  kept_ = BatchKept{};
+  if (o.keep_path_counts) kept_.counts.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), 0.0);
+  if (o.keep_levels) kept_.levels.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), kUnreached);
+  if (o.keep_parents) kept_.parents.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.part), -1);
+  if (o.validate) out.violations.assign(static_cast<size_t>(k) * kMsCheckCounters, 0);
   double ms = 0.0, check_ms = 0.0;
   bool dep_zeroed = false;
   for (int pass = 0; pass < out.passes; ++pass) {
     const int64_t first = static_cast<int64_t>(pass) * kMsSources;
     const int kp = static_cast<int>(std::min<int64_t>(kMsSources, k - first));
-    if (batch_pending_first_ >= 0) {  // (outside the timed window)
-      collect_batch_levels(batch_pending_first_, batch_pending_k_);
-      batch_pending_first_ = -1;
-    }
+    const int64_t* src = sources.data() + first;
+    collect_batch_levels();  // (the pass before: outside the timed window)
     out.discovered.resize(static_cast<size_t>(first + kp));
     out.reached.resize(static_cast<size_t>(first + kp), 0);
     out.edges.resize(static_cast<size_t>(first + kp), 0);
@@ -299,120 +308,114 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, BatchDirectio
     comm_.barrier();
     const auto t0 = std::chrono::steady_clock::now();
     const bool wide = ms_ && ms_->wide;
-    int lvl_bytes = keep_levels ? (wide ? 2 : 1) : 0;
-    if (run_batch_pass(sources.data() + first, kp, pass, dir, lvl_bytes, out) != 0) {
+    int lvl_bytes = o.keep_levels ? (wide ? 2 : 1) : 0;
+    if (run_batch_pass(src, kp, pass, o.direction, lvl_bytes, out) != 0) {
       // deeper than one-byte levels hold (or, without a level matrix, than
       // 16-bit ones would): once more with 16-bit levels, both runs timed
       ms_->wide = true;
       lvl_bytes = 2;
-      const int again = run_batch_pass(sources.data() + first, kp, pass, dir, lvl_bytes, out);
+      const int again = run_batch_pass(src, kp, pass, o.direction, lvl_bytes, out);
       DBFS_CHECK(again == 0, "run_batch: the 16-bit rerun overflowed");
     }
-    if (lvl_bytes == 2) out.wide_levels = true;
+    if (lvl_bytes > 1) out.wide_levels = true;
     be_.synchronize();
     const auto t1 = std::chrono::steady_clock::now();
-    ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    ms += ms_since(t0);
     check_device();  // (checked build: a violation a kernel of the pass recorded fails the batch)
-    if (keep_levels) {
-      batch_pending_first_ = first;
-      batch_pending_k_ = kp;
-      batch_last_k_ = kp;
+    if (o.keep_levels) {
+      kept_.pending_first = first;
+      kept_.pending_k = kp;
+      kept_.last_k = kp;
     }
-    if (validate || keep_parents) {
-      // (after the timed window, before the next pass reuses the matrix; a
-      // pass rerun with 16-bit levels is checked here once, on the rerun's)
-      check_batch_pass(sources.data() + first, kp,
-                       validate ? out.violations.data() + static_cast<size_t>(first) * kMsCheckCounters : nullptr,
-                       keep_parents, first);
-      check_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    if (!check && !bc) continue;
+    // After the timed window, before the next pass reuses the matrix (a rerun
+    // pass: once, on the rerun's), resolved once (`gathered` ends with the
+    // pass) for the check and then the betweenness sweep, each timed on its own.
+    const auto tg = std::chrono::steady_clock::now();
+    DBuf<uint8_t> gathered;
+    const MsPassMatrix m = pass_matrix(src, kp, gathered);
+    const double gather_ms = check ? 0.0 : ms_since(tg);  // (the all-gather: in check_ms when a check runs)
+    if (check) {
+      check_batch_pass(m, o.validate ? out.violations.data() + static_cast<size_t>(first) * kMsCheckCounters : nullptr,
+                       o.keep_parents, first);
+      check_ms += ms_since(t1);
     }
-    if (betweenness || keep_path_counts) {
-      // (as the check: after the timed window, on the rerun's matrix when the
-      // pass was repeated, before the next pass reuses it; timed on its own)
-      if (betweenness && !dep_zeroed) {
+    if (bc) {
+      out.bc_forward_ms += gather_ms;
+      out.bc_ms += gather_ms;
+      if (o.betweenness && !dep_zeroed) {
         if (ms_->bc_dep.size() == 0) ms_->bc_dep = DBuf<double>(be_, static_cast<size_t>(part_.part));
         be_.memset_async(ms_->bc_dep.data(), 0, ms_->bc_dep.bytes());
         dep_zeroed = true;
       }
       int depth = 0;
       for (int t = 0; t < kp; ++t) depth = std::max(depth, out.depth[static_cast<size_t>(first + t)]);
-      bc_batch_pass(sources.data() + first, kp, depth, betweenness, keep_path_counts, first, out);
+      bc_batch_pass(m, depth, o.betweenness, o.keep_path_counts, first, out);
     }
   }
   out.ms = comm_.max_host(ms);
-  if (validate || keep_parents) out.check_ms = comm_.max_host(check_ms);
-  if (betweenness || keep_path_counts) {
+  if (check) out.check_ms = comm_.max_host(check_ms);
+  if (bc) {
     out.bc_forward_ms = comm_.max_host(out.bc_forward_ms);
     out.bc_backward_ms = comm_.max_host(out.bc_backward_ms);
     out.bc_ms = comm_.max_host(out.bc_ms);
   }
-  if (betweenness) batch_dep_valid_ = true;
-  if (keep_path_counts) batch_counts_k_ = k;
-  if (keep_parents) batch_parents_k_ = k;
+  kept_.dep_valid = o.betweenness;
+  if (o.keep_path_counts) kept_.counts_k = k;
+  if (o.keep_parents) kept_.parents_k = k;
   int64_t edges = 0;
   for (int64_t e : out.edges) edges += e;
   out.gteps = out.ms > 0 ? static_cast<double>(edges) / (out.ms * 1e6) : 0.0;
-  if (keep_levels) batch_k_ = k;
+  if (o.keep_levels) kept_.k = k;
   return out;
 }
 
-// The level matrix of the pass just run -> rows [first, first + k) of batch_levels_.
-void Engine::collect_batch_levels(int64_t first, int k) {
+MsPassMatrix Engine::pass_matrix(const int64_t* src, int k, DBuf<uint8_t>& gathered) {
   const int P = part_.nranks;
-  const int64_t W = part_.part, n = part_.n;
   MsBuffers& b = *ms_;
-  const size_t bytes = static_cast<size_t>(W) * kMsSources * b.lvl_bytes;
-  std::vector<uint8_t> hb(bytes * P);
+  DBFS_CHECK(b.lvl_bytes != 0, "batch pass: no level matrix is resident");
+  MsPassMatrix m;
+  m.lvl = b.lvl.data();
   if (P > 1) {
-    DBuf<uint8_t> all(be_, bytes * P);
-    comm_.allgather(b.lvl.data(), all.data(), bytes);
-    be_.to_host(hb.data(), all.data(), hb.size());
-  } else {
-    be_.to_host(hb.data(), b.lvl.data(), bytes);
+    const size_t bytes = static_cast<size_t>(part_.part) * kMsSources * b.lvl_bytes;
+    gathered = DBuf<uint8_t>(be_, bytes * P);
+    comm_.allgather(b.lvl.data(), gathered.data(), bytes);
+    m.lvl = gathered.data();
   }
-  // (slices are W vertices each, so global vertex v is row v of the gathered matrix)
-  for (int t = 0; t < k; ++t) {
-    lvl_t* row = batch_levels_.data() + static_cast<size_t>(first + t) * static_cast<size_t>(n);
-    if (b.lvl_bytes == 2) {
-      const uint16_t* m = reinterpret_cast<const uint16_t*>(hb.data());
-      for (int64_t v = 0; v < n; ++v) {
-        const uint16_t x = m[v * kMsSources + t];
-        row[v] = x == kMsUnreached16 ? kUnreached : static_cast<lvl_t>(x);
-      }
-    } else {
-      for (int64_t v = 0; v < n; ++v) {
-        const uint8_t x = hb[static_cast<size_t>(v) * kMsSources + t];
-        row[v] = x == kMsUnreached8 ? kUnreached : static_cast<lvl_t>(x);
-      }
-    }
-  }
+  m.lvl_bytes = b.lvl_bytes;
+  m.lvl_rows = part_.part * P;
+  m.k = k;
+  std::copy(src, src + k, m.src);
+  m.batch_mask = ms_batch_mask(k);
+  return m;
 }
 
-// Backend::ms_check on the pass's matrix (several ranks: the all-gathered
-// slices, W vertices each, so global vertex v is row v -- the simple form, as
-// the rest of the several-rank batch).  A directed graph is checked by the
+// The level matrix of the last pass, if not collected yet -> its rows of kept_.levels.
+void Engine::collect_batch_levels() {
+  if (kept_.pending_first < 0) return;
+  const int64_t n = part_.n;
+  DBuf<uint8_t> gathered;
+  const MsPassMatrix m = pass_matrix(nullptr, 0, gathered);  // (the matrix alone; a gather of its own, deferred)
+  lvl_t* const rows = kept_.levels.data() + static_cast<size_t>(kept_.pending_first) * static_cast<size_t>(n);
+  ms_level_type(m.lvl_bytes, [&](auto l) {
+    using L = decltype(l);
+    copy_transposed(be_, static_cast<const L*>(m.lvl), n, kept_.pending_k, rows, static_cast<size_t>(n),
+                    [](L x) { return x == ms_unreached<L>() ? kUnreached : static_cast<lvl_t>(x); });
+  });
+  kept_.pending_first = -1;
+}
+
+// Backend::ms_check on the pass's matrix.  A directed graph is checked by the
 // directed rules in one walk over its in-edge shard, where every stored entry
 // u -> v appears once, in v's row.
-void Engine::check_batch_pass(const int64_t* src, int k, int64_t* viol, bool parents, int64_t first) {
+void Engine::check_batch_pass(const MsPassMatrix& m, int64_t* viol, bool parents, int64_t first) {
   const int P = part_.nranks;
   const int64_t W = part_.part;
   MsBuffers& b = *ms_;
-  DBFS_CHECK(b.lvl_bytes != 0, "batch check: no level matrix is resident");
-  const size_t bytes = static_cast<size_t>(W) * kMsSources * b.lvl_bytes;
-  DBuf<uint8_t> all;
-  if (P > 1) {
-    all = DBuf<uint8_t>(be_, bytes * P);
-    comm_.allgather(b.lvl.data(), all.data(), bytes);
-  }
   MsCheckArgs ca;
   ca.g = check_view();
   ca.directed = opt_.directed;
-  ca.lvl = P > 1 ? all.data() : b.lvl.data();
-  ca.lvl_bytes = b.lvl_bytes;
-  ca.lvl_rows = W * P;
-  ca.k = k;
-  std::copy(src, src + k, ca.src);
-  ca.batch_mask = k == kMsSources ? ~word_t(0) : (word_t(1) << k) - 1;
+  ca.m = m;
   if (viol) {
     if (b.check.size() == 0) b.check = DBuf<int64_t>(be_, kMsSources * kMsCheckCounters);
     be_.memset_async(b.check.data(), 0, b.check.bytes());
@@ -427,51 +430,29 @@ void Engine::check_batch_pass(const int64_t* src, int k, int64_t* viol, bool par
     if (P > 1) comm_.allreduce_sum_i64(b.check.data(), kMsSources * kMsCheckCounters);
     int64_t h[kMsSources * kMsCheckCounters];
     be_.to_host(h, b.check.data(), sizeof(h));
-    std::copy(h, h + static_cast<size_t>(k) * kMsCheckCounters, viol);
+    std::copy(h, h + static_cast<size_t>(m.k) * kMsCheckCounters, viol);
   }
-  if (parents) {
-    // vertex-major on the device, source-major on the host: copied and
-    // transposed kChunk rows at a time (a 16 MB host temporary, not rows x 256 B)
-    constexpr int64_t kChunk = int64_t(1) << 16;
-    const int64_t rows = g_.rows();
-    std::vector<uint32_t> hp(static_cast<size_t>(std::min(rows, kChunk)) * kMsSources);
-    int64_t* const base = batch_parents_.data() + static_cast<size_t>(first) * static_cast<size_t>(W);
-    for (int64_t r0 = 0; r0 < rows; r0 += kChunk) {
-      const int64_t nr = std::min(kChunk, rows - r0);
-      be_.to_host(hp.data(), b.par.data() + static_cast<size_t>(r0) * kMsSources,
-                  static_cast<size_t>(nr) * kMsSources * sizeof(uint32_t));
-      for (int64_t r = 0; r < nr; ++r) {
-        const uint32_t* line = hp.data() + static_cast<size_t>(r) * kMsSources;
-        for (int t = 0; t < k; ++t)
-          base[static_cast<size_t>(t) * static_cast<size_t>(W) + static_cast<size_t>(r0 + r)] =
-              line[t] == kMsNoParent ? -1 : static_cast<int64_t>(line[t]);
-      }
-    }
-  }
+  if (parents)
+    copy_transposed(be_, b.par.data(), g_.rows(), m.k,
+                    kept_.parents.data() + static_cast<size_t>(first) * static_cast<size_t>(W), static_cast<size_t>(W),
+                    [](uint32_t x) { return x == kMsNoParent ? int64_t(-1) : static_cast<int64_t>(x); });
   be_.synchronize();  // (a rank that copied nothing back: check_ms still ends with the work done)
   check_device();
 }
 
 // Backend::ms_bc_* on the pass's matrix: the sources' path counts level by
 // level outwards, then (accumulate) the dependencies from the deepest level
-// back, each level one launch.  Several ranks, the simple form: the level
-// matrix all-gathered as for the check, the value matrix replicated and the
-// owned lines all-gathered into it after every launch.  A directed graph's
-// forward sweep walks the in-edge shard, the backward one the out-edges.
-void Engine::bc_batch_pass(const int64_t* src, int k, int depth, bool accumulate, bool counts, int64_t first,
+// back, each level one launch.  Several ranks, the simple form: the value
+// matrix replicated and the owned lines all-gathered into it after every
+// launch.  A directed graph's forward sweep walks the in-edge shard, the
+// backward one the out-edges.
+void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bool counts, int64_t first,
                            BatchResult& out) {
   const auto t0 = std::chrono::steady_clock::now();
   const int P = part_.nranks;
   const int64_t W = part_.part, n = part_.n;
   MsBuffers& b = *ms_;
-  DBFS_CHECK(b.lvl_bytes != 0, "batch betweenness: no level matrix is resident");
-  const size_t lvl_bytes = static_cast<size_t>(W) * kMsSources * b.lvl_bytes;
   const size_t own_vals = static_cast<size_t>(W) * kMsSources;
-  DBuf<uint8_t> all;
-  if (P > 1) {
-    all = DBuf<uint8_t>(be_, lvl_bytes * P);
-    comm_.allgather(b.lvl.data(), all.data(), lvl_bytes);
-  }
   if (b.bc_val.size() == 0) {
     b.bc_val = DBuf<double>(be_, own_vals * P);
     if (P > 1) b.bc_own = DBuf<double>(be_, own_vals);
@@ -480,15 +461,10 @@ void Engine::bc_batch_pass(const int64_t* src, int k, int depth, bool accumulate
   be_.memset_async(b.bc_walked.data(), 0, b.bc_walked.bytes());
   MsBcArgs a;
   a.g = g_.view();
-  a.lvl = P > 1 ? all.data() : b.lvl.data();
-  a.lvl_bytes = b.lvl_bytes;
-  a.lvl_rows = W * P;
+  a.m = m;
   a.val = b.bc_val.data();
   a.own = P > 1 ? b.bc_own.data() : b.bc_val.data();
   a.dep = accumulate ? b.bc_dep.data() : nullptr;
-  a.k = k;
-  std::copy(src, src + k, a.src);
-  a.batch_mask = k == kMsSources ? ~word_t(0) : (word_t(1) << k) - 1;
   a.walked = b.bc_walked.data();
   // the long rows of a view, listed once per engine and threshold
   auto long_rows = [&](int which, const ShardView& view) {
@@ -531,21 +507,9 @@ void Engine::bc_batch_pass(const int64_t* src, int k, int depth, bool accumulate
     ++out.bc_launches;
   }
   if (fault_.kind == "bc_device" && fault_.rank == comm_.rank()) be_.inject_device_check();
-  if (counts) {
-    // vertex-major on the device, source-major on the host (as the parents)
-    constexpr int64_t kChunk = int64_t(1) << 14;
-    std::vector<double> hv(static_cast<size_t>(std::min(n, kChunk)) * kMsSources);
-    double* const base = batch_counts_.data() + static_cast<size_t>(first) * static_cast<size_t>(n);
-    for (int64_t v0 = 0; v0 < n; v0 += kChunk) {
-      const int64_t nv = std::min(kChunk, n - v0);
-      be_.to_host(hv.data(), b.bc_val.data() + static_cast<size_t>(v0) * kMsSources,
-                  static_cast<size_t>(nv) * kMsSources * sizeof(double));
-      for (int64_t v = 0; v < nv; ++v)
-        for (int t = 0; t < k; ++t)
-          base[static_cast<size_t>(t) * static_cast<size_t>(n) + static_cast<size_t>(v0 + v)] =
-              hv[static_cast<size_t>(v) * kMsSources + t];
-    }
-  }
+  if (counts)
+    copy_transposed(be_, b.bc_val.data(), n, m.k, kept_.counts.data() + static_cast<size_t>(first) * static_cast<size_t>(n),
+                    static_cast<size_t>(n), [](double x) { return x; });
   be_.synchronize();
   const auto t1 = std::chrono::steady_clock::now();
   if (accumulate) {
@@ -577,7 +541,7 @@ void Engine::bc_batch_pass(const int64_t* src, int k, int depth, bool accumulate
 }
 
 std::vector<double> Engine::gather_betweenness() {
-  DBFS_CHECK(batch_dep_valid_ && ms_, "gather_betweenness: no batch has run with betweenness");
+  DBFS_CHECK(kept_.dep_valid && ms_, "gather_betweenness: no batch has run with betweenness");
   const int P = part_.nranks;
   const int64_t W = part_.part, n = part_.n;
   std::vector<double> h(static_cast<size_t>(W) * P);
@@ -593,29 +557,30 @@ std::vector<double> Engine::gather_betweenness() {
 }
 
 std::vector<double> Engine::gather_batch_path_counts() {
-  DBFS_CHECK(batch_counts_k_ > 0, "gather_batch_path_counts: no batch has run with keep_path_counts");
-  return batch_counts_;
+  DBFS_CHECK(kept_.counts_k > 0, "gather_batch_path_counts: no batch has run with keep_path_counts");
+  return kept_.counts;
 }
 
 std::vector<int64_t> Engine::validate_batch_pass(const std::vector<int64_t>& sources) {
-  DBFS_CHECK(ms_ && batch_last_k_ > 0 && ms_->lvl_bytes != 0,
+  DBFS_CHECK(ms_ && kept_.last_k > 0 && ms_->lvl_bytes != 0,
              "validate_batch_pass: no batch has run with keep_levels");
-  DBFS_CHECK(static_cast<int>(sources.size()) == batch_last_k_,
-             "validate_batch_pass: expected as many sources as the last pass had (" + std::to_string(batch_last_k_) +
+  DBFS_CHECK(static_cast<int>(sources.size()) == kept_.last_k,
+             "validate_batch_pass: expected as many sources as the last pass had (" + std::to_string(kept_.last_k) +
                  "), got " + std::to_string(sources.size()));
   for (int64_t v : sources) DBFS_CHECK(v >= 0 && v < part_.n, "validate_batch_pass: source vertex out of range");
   std::vector<int64_t> viol(sources.size() * kMsCheckCounters, 0);
-  check_batch_pass(sources.data(), batch_last_k_, viol.data(), false, 0);
+  DBuf<uint8_t> gathered;  // (resolved afresh: debug_set_batch_level may have changed the matrix)
+  check_batch_pass(pass_matrix(sources.data(), kept_.last_k, gathered), viol.data(), false, 0);
   return viol;
 }
 
 void Engine::debug_set_batch_level(int slot, int64_t vertex, int level) {
-  DBFS_CHECK(ms_ && batch_last_k_ > 0 && ms_->lvl_bytes != 0,
+  DBFS_CHECK(ms_ && kept_.last_k > 0 && ms_->lvl_bytes != 0,
              "debug_set_batch_level: no batch has run with keep_levels");
   DBFS_CHECK(slot >= 0 && slot < kMsSources && vertex >= 0 && vertex < part_.n,
              "debug_set_batch_level: slot or vertex out of range");
   MsBuffers& b = *ms_;
-  const int none = b.lvl_bytes == 2 ? kMsUnreached16 : kMsUnreached8;
+  const int none = ms_unreached(b.lvl_bytes);
   DBFS_CHECK(level < none, "debug_set_batch_level: the level does not fit the matrix");
   const int64_t r = vertex - g_.lo();
   if (r < 0 || r >= g_.rows()) return;  // another rank's
@@ -625,16 +590,16 @@ void Engine::debug_set_batch_level(int slot, int64_t vertex, int level) {
 }
 
 std::vector<int64_t> Engine::gather_batch_parents() {
-  DBFS_CHECK(batch_parents_k_ > 0, "gather_batch_parents: no batch has run with keep_parents");
+  DBFS_CHECK(kept_.parents_k > 0, "gather_batch_parents: no batch has run with keep_parents");
   const int P = part_.nranks;
-  const int64_t W = part_.part, n = part_.n, k = batch_parents_k_;
+  const int64_t W = part_.part, n = part_.n, k = kept_.parents_k;
   std::vector<int64_t> out(static_cast<size_t>(k) * static_cast<size_t>(n));
   std::vector<int64_t> all;
-  const int64_t* slices = batch_parents_.data();  // [rank][k][W]
+  const int64_t* slices = kept_.parents.data();  // [rank][k][W]
   if (P > 1) {
     const size_t cnt = static_cast<size_t>(k) * static_cast<size_t>(W);
     DBuf<int64_t> send(be_, cnt), recv(be_, cnt * P);
-    be_.to_device(send.data(), batch_parents_.data(), cnt * sizeof(int64_t));
+    be_.to_device(send.data(), kept_.parents.data(), cnt * sizeof(int64_t));
     comm_.allgather(send.data(), recv.data(), cnt * sizeof(int64_t));
     all.resize(cnt * P);
     be_.to_host(all.data(), recv.data(), all.size() * sizeof(int64_t));
@@ -649,12 +614,9 @@ std::vector<int64_t> Engine::gather_batch_parents() {
 }
 
 std::vector<lvl_t> Engine::gather_batch_levels() {
-  DBFS_CHECK(batch_k_ > 0, "gather_batch_levels: no batch has run with keep_levels");
-  if (batch_pending_first_ >= 0) {
-    collect_batch_levels(batch_pending_first_, batch_pending_k_);
-    batch_pending_first_ = -1;
-  }
-  return batch_levels_;
+  DBFS_CHECK(kept_.k > 0, "gather_batch_levels: no batch has run with keep_levels");
+  collect_batch_levels();
+  return kept_.levels;
 }
 
 }  // namespace dbfs

@@ -1021,8 +1021,23 @@ constexpr int kMsStats = 2 + kMsSources;
 // workgroups of an ms kernel at most (they stride over their work; one totals
 // slot of kMsStats entries each)
 constexpr int kMsMaxGrid = 1024;
-// level matrix entries that read unreached (u8 / u16 levels)
-constexpr int kMsUnreached8 = 0xFF, kMsUnreached16 = 0xFFFF;
+// f(L{}) with the level type of lvl_bytes (2: uint16_t, else uint8_t): the one
+// place that turns the width into a type, for the launchers and the host alike.
+template <class F>
+decltype(auto) ms_level_type(int lvl_bytes, F&& f) {
+  if (lvl_bytes == 2) return f(uint16_t{});
+  return f(uint8_t{});
+}
+// The level matrix entry that reads unreached: all ones.
+template <class L>
+DBFS_HD constexpr int ms_unreached() {
+  return static_cast<int>(static_cast<L>(~static_cast<L>(0)));
+}
+inline int ms_unreached(int lvl_bytes) {
+  return ms_level_type(lvl_bytes, [](auto l) { return ms_unreached<decltype(l)>(); });
+}
+// bit s set: s < k
+DBFS_HD word_t ms_batch_mask(int k) { return k == kMsSources ? ~word_t(0) : (word_t(1) << k) - 1; }
 
 // Host-mapped totals of a batch level (as StatsMailbox: values first, then seq).
 struct MsMailbox {
@@ -1112,12 +1127,29 @@ struct MsDegreeArgs {
   int64_t* deg_sum = nullptr;  // kMsSources, zero on entry
 };
 
+// A finished pass's level matrix and its sources: what the check and the
+// betweenness sweeps read (Engine::pass_matrix).  `lvl` is the full matrix:
+// row v holds the kMsSources levels of global vertex v (one rank: the pass's
+// own matrix; several: the all-gathered slices), all ones = unreached.
+struct MsPassMatrix {
+  const void* lvl = nullptr;
+  int lvl_bytes = 1;
+  int64_t lvl_rows = 0;          // rows of `lvl` (>= n: the checked build's bound on column ids)
+  int k = 0;
+  int64_t src[kMsSources] = {};  // global vertex ids
+  word_t batch_mask = 0;         // ms_batch_mask(k)
+};
+// lvl[v][s] on the host (the CPU backend's loops).
+inline int level_at(const MsPassMatrix& m, int64_t v, int s) {
+  return ms_level_type(m.lvl_bytes, [&](auto l) -> int {
+    return static_cast<const decltype(l)*>(m.lvl)[v * kMsSources + s];
+  });
+}
+
 // Graph500-style check of a finished pass's level matrix, all sources at once
 // (ValidateArgs' rules per source; Engine::run_batch validate / keep_parents).
-// `lvl` is the full matrix: row v holds the kMsSources levels of global vertex
-// v (one rank: the pass's own matrix; several: the all-gathered slices), all
-// ones = unreached.  Over the directed adjacency entries (u, w) of the owned
-// rows, for every source s < k:
+// Over the directed adjacency entries (u, w) of the owned rows, for every
+// source s < m.k:
 //   count form (out):  out[3 s + 0] += entries with both ends reached and
 //     |lvl[u][s] - lvl[w][s]| > 1 (gap), out[3 s + 1] += entries with exactly
 //     one end reached (cross), out[3 s + 2] += reached u != src[s] without a
@@ -1136,20 +1168,15 @@ constexpr int kMsCheckCounters = 3;
 constexpr uint32_t kMsNoParent = 0xFFFFFFFFu;
 struct MsCheckArgs {
   ShardView g;
-  const void* lvl = nullptr;
-  int lvl_bytes = 1;
-  int64_t lvl_rows = 0;          // rows of `lvl` (>= n: the checked build's bound on column ids)
-  int k = 0;
-  int64_t src[kMsSources] = {};  // global vertex ids
-  word_t batch_mask = 0;         // bit s set: s < k
+  MsPassMatrix m;
   int64_t* out = nullptr;        // kMsSources x kMsCheckCounters, accumulated; nullptr: no counts
   uint32_t* par = nullptr;       // owned rows x kMsSources; nullptr: no parents
   bool directed = false;
 };
 
 // Shortest-path counts and Brandes dependencies of a finished pass, all its
-// sources at once (Engine::run_batch betweenness / keep_path_counts).  `lvl` is
-// the pass's full level matrix as in MsCheckArgs; `val` is a matrix of doubles
+// sources at once (Engine::run_batch betweenness / keep_path_counts).  `m` is
+// the pass's full level matrix (MsPassMatrix); `val` is a matrix of doubles
 // of the same shape (row v: the kMsSources values of global vertex v) and
 // `own` the lines of the owned rows, which a launch writes (one rank: val
 // itself; several: a buffer of its own, all-gathered into every rank's val
@@ -1179,15 +1206,10 @@ struct MsBcArgs {
   const eid_t* row_off = nullptr;   // the rows this launch walks (local offsets, global column ids)
   const vid_t* col = nullptr;
   int64_t nnz = 0;                  // entries of `col` (the checked build's bound)
-  const void* lvl = nullptr;
-  int lvl_bytes = 1;
-  int64_t lvl_rows = 0;             // rows of lvl and val (>= n)
+  MsPassMatrix m;                   // (val has m.lvl_rows rows too)
   double* val = nullptr;            // (written by ms_bc_init and the all-gathers only)
   double* own = nullptr;            // g.rows x kMsSources
   double* dep = nullptr;            // g.rows (backward)
-  int k = 0;
-  int64_t src[kMsSources] = {};     // global vertex ids
-  word_t batch_mask = 0;            // bit s set: s < k
   int level = 0;
   bool leaf = false;
   unsigned long long* walked = nullptr;

@@ -458,6 +458,14 @@ struct RunResult {
 enum class BatchDirection { Auto, Push, Pull, Alternate };
 BatchDirection parse_batch_direction(const std::string& s);
 
+// What a batch does besides the traversal (Engine::run_batch describes each).
+struct BatchOptions {
+  BatchDirection direction = BatchDirection::Auto;
+  bool keep_levels = true;
+  bool validate = false, keep_parents = false;
+  bool betweenness = false, keep_path_counts = false;
+};
+
 // One level of one pass: form 'P' push, 'L' pull; the active vertices it
 // expanded and the sum of their degrees (global).
 struct BatchLevelRecord {
@@ -489,7 +497,9 @@ struct BatchResult {
   // over ranks (all must be 0); empty when not asked for
   std::vector<int64_t> violations;
   // wall time of the per-pass checks (validate / keep_parents; max over
-  // ranks): after each pass's timed window, never part of `ms`
+  // ranks): after each pass's timed window, never part of `ms`.  Several
+  // ranks: the all-gather of the pass's level matrix is part of it (without a
+  // check: of bc_ms and bc_forward_ms)
   double check_ms = 0.0;
   // run_batch(betweenness / keep_path_counts): wall time of the per-pass path
   // counts and dependency accumulation (max over ranks), after each pass's
@@ -550,9 +560,7 @@ class Engine {
   // bytes on the host).  Both need keep_levels; BatchResult::bc_ms.  Several
   // ranks: the simple form -- the value matrix is replicated and the owned
   // lines are all-gathered after every launch.
-  BatchResult run_batch(const std::vector<int64_t>& sources, BatchDirection dir = BatchDirection::Auto,
-                        bool keep_levels = true, bool validate = false, bool keep_parents = false,
-                        bool betweenness = false, bool keep_path_counts = false);
+  BatchResult run_batch(const std::vector<int64_t>& sources, const BatchOptions& o = {});
   // The last batch's dependency sums, one per vertex: dep(v) = the sum over the
   // source slots i with v != src_i of delta_{src_i}(v) -- raw: not halved on
   // an undirected graph, not rescaled, not normalised; collective.  Throws
@@ -562,7 +570,7 @@ class Engine {
   // does not reach; exact while below 2^53).  Throws when the batch ran
   // without keep_path_counts.
   std::vector<double> gather_batch_path_counts();
-  int64_t batch_path_count_sources() const { return batch_counts_k_; }  // (-1: none)
+  int64_t batch_path_count_sources() const { return kept_.counts_k; }  // (-1: none)
   // The last batch's levels, [k][n] row-major, kUnreached where source k does
   // not reach; collective.  Throws when the batch ran without keep_levels.
   std::vector<lvl_t> gather_batch_levels();
@@ -574,7 +582,7 @@ class Engine {
   // convention per source (parent[src] = src, -1 unreached); collective.
   // Throws when the batch ran without keep_parents.
   std::vector<int64_t> gather_batch_parents();
-  int64_t batch_parent_sources() const { return batch_parents_k_; }  // of the last batch with parents (-1: none)
+  int64_t batch_parent_sources() const { return kept_.parents_k; }  // of the last batch with parents (-1: none)
   // The count form of the check once more, on the level matrix still resident
   // from the last pass of the last batch, against `sources` (as many as that
   // pass had, at most 64): [k][3] as BatchResult::violations; collective.
@@ -587,7 +595,7 @@ class Engine {
   // owner; level < 0: unreached), so a test can plant a violation for
   // validate() and parents_local() to find.
   void debug_set_level(int64_t vertex, int level);
-  int64_t batch_sources() const { return batch_k_; }  // of the last batch with levels (-1: none)
+  int64_t batch_sources() const { return kept_.k; }  // of the last batch with levels (-1: none)
   int64_t global_directed_edges() const { return total_directed_; }
   const EngineOptions& options() const { return opt_; }
   void set_options(const EngineOptions& o) {
@@ -731,31 +739,37 @@ class Engine {
   std::unique_ptr<MsBuffers> ms_;
   // 0: done; 1: deeper than the level type holds (rerun wider)
   int run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out);
-  void collect_batch_levels(int64_t first, int k);
+  void collect_batch_levels();
   // the view a level check walks: the in-edge shard of a directed graph
   // (built on first use), the shard itself otherwise
   ShardView check_view();
-  std::vector<lvl_t> batch_levels_;      // [k][n], passes collected so far
-  int64_t batch_k_ = -1;                 // sources of the last batch (-1: none, or without levels)
-  int64_t batch_pending_first_ = -1;     // last pass not collected yet: its first source ...
-  int batch_pending_k_ = 0;              // ... and size
-  // The check of the pass just run (sources src[0..k)): counts into viol
-  // ([k][3], or nullptr), parents into rows [first, first + k) of
-  // batch_parents_ (parents set).  Blocking.
-  void check_batch_pass(const int64_t* src, int k, int64_t* viol, bool parents, int64_t first);
-  int batch_last_k_ = 0;                 // sources of the last pass whose level matrix is resident (0: none)
-  // Path counts and dependencies of the pass just run (sources src[0..k), the
-  // deepest of them `depth` levels): dependencies into MsBuffers::bc_dep
-  // (accumulate), path counts into rows [first, first + k) of batch_counts_
-  // (counts).  Blocking; the forward and backward times are added to `out`.
-  void bc_batch_pass(const int64_t* src, int k, int depth, bool accumulate, bool counts, int64_t first,
-                     BatchResult& out);
-  bool batch_dep_valid_ = false;         // the last batch accumulated dependencies
-  std::vector<double> batch_counts_;     // [k][n]
-  int64_t batch_counts_k_ = -1;          // sources of the last batch with path counts (-1: none)
-  // owned slices of the parent trees, [k][part] (-1: unreached or padding)
-  std::vector<int64_t> batch_parents_;
-  int64_t batch_parents_k_ = -1;         // sources of the last batch with parents (-1: none)
+  // What the last batch left, and what of its last pass is still resident.
+  struct BatchKept {
+    int64_t k = -1;              // sources of the last batch (-1: none, or without levels)
+    std::vector<lvl_t> levels;   // [k][n], passes collected so far
+    int64_t pending_first = -1;  // last pass not collected yet: its first source ...
+    int pending_k = 0;           // ... and size
+    int last_k = 0;              // sources of the last pass whose level matrix is resident (0: none)
+    // owned slices of the parent trees, [k][part] (-1: unreached or padding)
+    std::vector<int64_t> parents;
+    int64_t parents_k = -1;      // sources of the last batch with parents (-1: none)
+    std::vector<double> counts;  // path counts, [k][n]
+    int64_t counts_k = -1;       // sources of the last batch with path counts (-1: none)
+    bool dep_valid = false;      // the last batch accumulated dependencies
+  };
+  BatchKept kept_;
+  // The resident pass's level matrix with its sources src[0..k): the pass's
+  // own (one rank), or the owned slices all-gathered into `gathered` (W
+  // vertices each, so global vertex v is row v: the several-rank simple form).
+  MsPassMatrix pass_matrix(const int64_t* src, int k, DBuf<uint8_t>& gathered);
+  // The check of the pass m: counts into viol ([k][3], or nullptr), parents
+  // into rows [first, first + k) of kept_.parents (parents set).  Blocking.
+  void check_batch_pass(const MsPassMatrix& m, int64_t* viol, bool parents, int64_t first);
+  // Path counts and dependencies of the pass m (the deepest of its sources
+  // `depth` levels): dependencies into MsBuffers::bc_dep (accumulate), path
+  // counts into rows [first, first + k) of kept_.counts (counts).  Blocking;
+  // the forward and backward times are added to `out`.
+  void bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bool counts, int64_t first, BatchResult& out);
   // reference-mode state
   bool ref_ready_ = false;
   DBuf<lvl_t> dist_;

@@ -8,26 +8,24 @@
 //                   sigma into the coefficient (1 + delta) / sigma, and the
 //                   vertex's share of the centrality vector
 //
-// Both walks have ms_check_kernel's shape (ms_kernels.hip): a wave per owned
-// vertex, striding over the rows; lane s is source s; the row is read 64
-// column ids per step and for each of them lane s loads lvl[w][s], with
-// kMsBcAhead of those scattered lines requested before the first is consumed.
+// Both sweeps walk as ms_check_kernel does (ms_kernels.hip): a wave per owned
+// vertex, striding over the rows; lane s is source s; the row's level lines
+// come from ms_walk_row (ms_walk.hpp), a group at a time.
 // A value line (512 B per vertex) is touched only by the lanes whose level
 // matches, and a vertex none of whose lanes sits on the launch's level is
 // skipped after its own level line, before its row offsets are read.
 // Every sum is pull-form and per lane in stored row order: no atomics on
 // floating-point values, the same bits on every run.
-#include "kernel_common.hpp"
+#include "ms_walk.hpp"
 
 namespace dbfs {
 namespace kern {
 namespace {
 
 constexpr int kMsBcBlock = 256;
-// Workgroups at most and lines in flight: ms_check_kernel's values (its
-// registers allow the same 8 waves per SIMD: profiles/ms_bfs_regs.txt).
+// Workgroups at most: ms_check_kernel's value (its registers allow the same
+// 8 waves per SIMD: profiles/ms_bfs_regs.txt).
 constexpr int kMsBcGrid = 2048;
-constexpr int kMsBcAhead = 8;
 
 // Sum over the wave in a fixed order (lane i + lane i ^ 32, then ^ 16 .. ^ 1;
 // every lane ends with the same bits).
@@ -39,10 +37,10 @@ __device__ __forceinline__ double wave_sum_f64(double x) {
 
 __global__ __launch_bounds__(kMsBcBlock) void ms_bc_init_kernel(MsBcArgs a) {
   const int lane = lane_id();
-  const int64_t my_src = ((a.batch_mask >> lane) & 1ull) ? a.src[lane] : -1;
+  const int64_t my_src = ((a.m.batch_mask >> lane) & 1ull) ? a.m.src[lane] : -1;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
   const int64_t first = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + (threadIdx.x >> 6);
-  for (int64_t v = first; v < a.lvl_rows; v += stride) a.val[v * kMsSources + lane] = v == my_src ? 1.0 : 0.0;
+  for (int64_t v = first; v < a.m.lvl_rows; v += stride) a.val[v * kMsSources + lane] = v == my_src ? 1.0 : 0.0;
   for (int64_t r = first; r < a.g.rows; r += stride) a.own[r * kMsSources + lane] = a.g.lo + r == my_src ? 1.0 : 0.0;
 }
 
@@ -51,34 +49,22 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_init_kernel(MsBcArgs a) {
 template <class L>
 __device__ __forceinline__ double ms_bc_row_sum(const MsBcArgs& a, const L* __restrict__ lvl, eid_t rs, eid_t re,
                                                 bool at, int want) {
-  constexpr int kNone = static_cast<int>(static_cast<L>(~static_cast<L>(0)));
+  constexpr int kNone = ms_unreached<L>();
   const double* __restrict__ val = a.val;
   const int lane = lane_id();
   double sum = 0.0;
-  for (eid_t e = rs; e < re; e += kWave) {
-    const int cnt = static_cast<int>(min(static_cast<eid_t>(kWave), re - e));
-    const vid_t mine = lane < cnt ? a.col[e + lane] : 0u;
-    DBFS_DCHECK(static_cast<int64_t>(mine) < a.lvl_rows, 28, mine);
-    for (int j = 0; j < cnt; j += kMsBcAhead) {
-      int64_t at_w[kMsBcAhead];
-      int lw[kMsBcAhead];
-      double x[kMsBcAhead];
+  ms_walk_row<L, kMsWalkAhead>(lvl, a.col, rs, re, a.m.lvl_rows, 28, [&](int valid, const vid_t* w, const int* lw) {
+    double x[kMsWalkAhead];  // (the group's value loads: issued together, after its level lines)
 #pragma unroll
-      for (int i = 0; i < kMsBcAhead; ++i) {
-        // (the last group of a row repeats its last entry's line instead of branching around the loads)
-        const vid_t w = static_cast<vid_t>(__builtin_amdgcn_readlane(static_cast<int>(mine), min(j + i, cnt - 1)));
-        at_w[i] = static_cast<int64_t>(w) * kMsSources + lane;
-        lw[i] = lvl[at_w[i]];
-      }
-#pragma unroll
-      for (int i = 0; i < kMsBcAhead; ++i) {
-        const bool valid = j + i < cnt;  // (wave-uniform)
-        x[i] = valid && at && lw[i] == want && lw[i] != kNone ? val[at_w[i]] : 0.0;
-      }
-#pragma unroll
-      for (int i = 0; i < kMsBcAhead; ++i) sum += x[i];  // (stored row order; + 0.0 changes no bit of a sum >= 0)
+    for (int i = 0; i < kMsWalkAhead; ++i) {
+      // (&, not &&: a branch on the wave-uniform i < valid would take the entry's level load along)
+      const bool take = (i < valid) & at & (lw[i] == want) & (lw[i] != kNone);
+      x[i] = take ? val[static_cast<int64_t>(w[i]) * kMsSources + lane] : 0.0;
     }
-  }
+#pragma unroll
+    for (int i = 0; i < kMsWalkAhead; ++i) sum += x[i];  // (stored row order; + 0.0 changes no bit of a sum >= 0)
+    return true;
+  });
   return sum;
 }
 
@@ -106,15 +92,15 @@ __device__ __forceinline__ void ms_bc_store_backward(const MsBcArgs& a, int64_t 
 template <class L>
 __global__ __launch_bounds__(kMsBcBlock) void ms_bc_forward_kernel(MsBcArgs a) {
   const ShardView& g = a.g;
-  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
+  const L* __restrict__ lvl = static_cast<const L*>(a.m.lvl);
   const int lane = lane_id();
-  const bool on = (a.batch_mask >> lane) & 1ull;  // lanes past the pass's sources are idle
+  const bool on = (a.m.batch_mask >> lane) & 1ull;  // lanes past the pass's sources are idle
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   unsigned long long walked = 0;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
   for (int64_t r = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + wave; r < g.rows; r += stride) {
     const int64_t v = g.lo + r;
-    DBFS_DCHECK(v < a.lvl_rows, 27, v);
+    DBFS_DCHECK(v < a.m.lvl_rows, 27, v);
     const bool at = on && static_cast<int>(lvl[v * kMsSources + lane]) == a.level;
     if (__ballot(at) == 0ull) continue;
     const eid_t rs = a.row_off[r], re = a.row_off[r + 1];
@@ -129,16 +115,16 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_forward_kernel(MsBcArgs a) {
 template <class L>
 __global__ __launch_bounds__(kMsBcBlock) void ms_bc_backward_kernel(MsBcArgs a) {
   const ShardView& g = a.g;
-  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
+  const L* __restrict__ lvl = static_cast<const L*>(a.m.lvl);
   const int lane = lane_id();
-  const bool on = (a.batch_mask >> lane) & 1ull;
-  const int64_t my_src = on ? a.src[lane] : -1;
+  const bool on = (a.m.batch_mask >> lane) & 1ull;
+  const int64_t my_src = on ? a.m.src[lane] : -1;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   unsigned long long walked = 0;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
   for (int64_t r = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + wave; r < g.rows; r += stride) {
     const int64_t v = g.lo + r;
-    DBFS_DCHECK(v < a.lvl_rows, 27, v);
+    DBFS_DCHECK(v < a.m.lvl_rows, 27, v);
     const bool at = on && static_cast<int>(lvl[v * kMsSources + lane]) == a.level;
     if (__ballot(at) == 0ull) continue;
     double acc = 0.0;
@@ -166,16 +152,16 @@ template <class L, bool kBackward>
 __global__ __launch_bounds__(kMsBcLongBlock) void ms_bc_long_kernel(MsBcArgs a) {
   __shared__ double s_part[kMsBcLongWaves][kWave];
   const ShardView& g = a.g;
-  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
+  const L* __restrict__ lvl = static_cast<const L*>(a.m.lvl);
   const int lane = lane_id();
-  const bool on = (a.batch_mask >> lane) & 1ull;
-  const int64_t my_src = on ? a.src[lane] : -1;
+  const bool on = (a.m.batch_mask >> lane) & 1ull;
+  const int64_t my_src = on ? a.m.src[lane] : -1;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   unsigned long long walked = 0;
   for (int64_t i = blockIdx.x; i < a.n_long; i += gridDim.x) {
     const int64_t r = a.long_rows[i];
     const int64_t v = g.lo + r;
-    DBFS_DCHECK(r < g.rows && v < a.lvl_rows, 30, r);
+    DBFS_DCHECK(r < g.rows && v < a.m.lvl_rows, 30, r);
     // (every wave reads the same line: the skip is uniform over the workgroup)
     const bool at = on && static_cast<int>(lvl[v * kMsSources + lane]) == a.level;
     if (__ballot(at) == 0ull) continue;
@@ -209,36 +195,29 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_long_rows_kernel(const eid_t
   }
 }
 
-template <class L, bool kBackward>
-void ms_bc_long_launch(const MsBcArgs& a, hipStream_t st) {
-  if (a.n_long <= 0) return;
-  ms_bc_long_kernel<L, kBackward><<<grid_for(a.n_long, 1, kMsBcGrid), kMsBcLongBlock, 0, st>>>(a);
+// One level of a sweep: the rows by their wave, then the long ones.
+template <bool kBackward>
+void ms_bc_sweep(const MsBcArgs& a, hipStream_t st) {
+  if (a.g.rows <= 0) return;
+  const unsigned grid = grid_for(a.g.rows, kMsBcBlock / kWave, kMsBcGrid);
+  ms_level_type(a.m.lvl_bytes, [&](auto l) {
+    using L = decltype(l);
+    if (kBackward) ms_bc_backward_kernel<L><<<grid, kMsBcBlock, 0, st>>>(a);
+    else ms_bc_forward_kernel<L><<<grid, kMsBcBlock, 0, st>>>(a);
+    if (a.n_long > 0)
+      ms_bc_long_kernel<L, kBackward><<<grid_for(a.n_long, 1, kMsBcGrid), kMsBcLongBlock, 0, st>>>(a);
+  });
 }
 
 }  // namespace
 
 void ms_bc_init(const MsBcArgs& a, hipStream_t st) {
-  if (a.lvl_rows <= 0) return;
-  ms_bc_init_kernel<<<grid_for(a.lvl_rows, kMsBcBlock / kWave, kMsBcGrid), kMsBcBlock, 0, st>>>(a);
+  if (a.m.lvl_rows <= 0) return;
+  ms_bc_init_kernel<<<grid_for(a.m.lvl_rows, kMsBcBlock / kWave, kMsBcGrid), kMsBcBlock, 0, st>>>(a);
 }
 
-void ms_bc_forward(const MsBcArgs& a, hipStream_t st) {
-  if (a.g.rows <= 0) return;
-  const unsigned grid = grid_for(a.g.rows, kMsBcBlock / kWave, kMsBcGrid);
-  if (a.lvl_bytes == 2) ms_bc_forward_kernel<uint16_t><<<grid, kMsBcBlock, 0, st>>>(a);
-  else ms_bc_forward_kernel<uint8_t><<<grid, kMsBcBlock, 0, st>>>(a);
-  if (a.lvl_bytes == 2) ms_bc_long_launch<uint16_t, false>(a, st);
-  else ms_bc_long_launch<uint8_t, false>(a, st);
-}
-
-void ms_bc_backward(const MsBcArgs& a, hipStream_t st) {
-  if (a.g.rows <= 0) return;
-  const unsigned grid = grid_for(a.g.rows, kMsBcBlock / kWave, kMsBcGrid);
-  if (a.lvl_bytes == 2) ms_bc_backward_kernel<uint16_t><<<grid, kMsBcBlock, 0, st>>>(a);
-  else ms_bc_backward_kernel<uint8_t><<<grid, kMsBcBlock, 0, st>>>(a);
-  if (a.lvl_bytes == 2) ms_bc_long_launch<uint16_t, true>(a, st);
-  else ms_bc_long_launch<uint8_t, true>(a, st);
-}
+void ms_bc_forward(const MsBcArgs& a, hipStream_t st) { ms_bc_sweep<false>(a, st); }
+void ms_bc_backward(const MsBcArgs& a, hipStream_t st) { ms_bc_sweep<true>(a, st); }
 
 void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
                      unsigned long long* count, hipStream_t st) {

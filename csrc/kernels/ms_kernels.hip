@@ -18,7 +18,7 @@
 // write-through, a ticket, the last workgroup sums them.
 #include <algorithm>
 
-#include "kernel_common.hpp"
+#include "ms_walk.hpp"
 
 namespace dbfs {
 namespace kern {
@@ -426,20 +426,14 @@ __global__ __launch_bounds__(kMsBlock) void ms_degree_kernel(MsDegreeArgs a) {
 }
 
 // ms_check (backend.hpp MsCheckArgs): a wave per owned vertex u, striding over
-// the rows; lane s is source s.  Lane s holds lvl[u][s] (the vertex's line of
-// the level matrix); the wave reads the row 64 column ids per step (lane i:
-// col[e + i], coalesced), and for each of them, made wave-uniform by a
-// readlane, lane s loads lvl[w][s]: one scattered 64-B line (128 B with 16-bit
-// levels) per adjacency entry, checked for all sources at once.  The walk is
-// bound by the latency of those lines, so kMsCheckAhead of them are requested
-// before the first is consumed (the last group of a row repeats its last
-// entry's line instead of branching around the loads).  Rows are walked in
-// stored order, so the parent form's first parent is the host loops' first.
+// the rows; lane s is source s and holds lvl[u][s] (the vertex's line of the
+// level matrix) against the lvl[w][s] of every entry w that ms_walk_row hands
+// over, all sources at once.  Rows are walked in stored order, so the parent
+// form's first parent is the host loops' first.
 // Workgroups at most (they stride over the rows): 2048 x 4 waves = 8192 waves, the 256 CUs x 4 SIMDs
 // x 8 waves the kernel's registers allow (profiles/ms_bfs_regs.txt) when the workgroups spread evenly
 // over the CUs; not tuned against other sizes.
 constexpr int kMsCheckGrid = 2048;
-constexpr int kMsCheckAhead = 8;
 
 // kDirected: g is the in-edge view, lane s holds lvl[v][s] of the row's vertex
 // v and every entry is a u with a stored u -> v: cross = u reached and v not,
@@ -448,16 +442,16 @@ template <class L, bool kCount, bool kParent, bool kDirected>
 __global__ __launch_bounds__(kMsBlock) void ms_check_kernel(MsCheckArgs a) {
   __shared__ unsigned long long s_cnt[kMsSources * kMsCheckCounters];
   const ShardView& g = a.g;
-  const L* __restrict__ lvl = static_cast<const L*>(a.lvl);
-  constexpr int kNone = static_cast<int>(static_cast<L>(~static_cast<L>(0)));
+  const L* __restrict__ lvl = static_cast<const L*>(a.m.lvl);
+  constexpr int kNone = ms_unreached<L>();
   const int t = threadIdx.x;
   const int lane = lane_id();
   if (kCount) {
     if (t < kMsSources * kMsCheckCounters) s_cnt[t] = 0ull;
     __syncthreads();
   }
-  const bool on = (a.batch_mask >> lane) & 1ull;  // lanes past the pass's sources count and store nothing
-  const int64_t my_src = on ? a.src[lane] : -1;
+  const bool on = (a.m.batch_mask >> lane) & 1ull;  // lanes past the pass's sources count and store nothing
+  const int64_t my_src = on ? a.m.src[lane] : -1;
   unsigned long long gap = 0, cross = 0, orphan = 0;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBlock / kWave);
@@ -465,52 +459,36 @@ __global__ __launch_bounds__(kMsBlock) void ms_check_kernel(MsCheckArgs a) {
     const int64_t u = g.lo + r;
     const eid_t rs = g.row_off[r], re = g.row_off[r + 1];
     DBFS_DCHECK(rs >= 0 && rs <= re && re <= g.nnz, 24, r);
-    DBFS_DCHECK(u < a.lvl_rows, 25, u);
+    DBFS_DCHECK(u < a.m.lvl_rows, 25, u);
     const int lu = lvl[u * kMsSources + lane];
     const bool ru = on && lu != kNone;
     const bool is_src = u == my_src;
     bool has_par = false;
     uint32_t par = kMsNoParent;
     // parents only: a row is walked while some lane still looks for its parent
-    bool walk = rs < re;
-    if (!kCount) walk = walk && __ballot(ru && !is_src) != 0ull;
-    for (eid_t e = rs; walk && e < re; e += kWave) {
-      const int cnt = static_cast<int>(min(static_cast<eid_t>(kWave), re - e));
-      const vid_t mine = lane < cnt ? g.col[e + lane] : 0u;
-      DBFS_DCHECK(static_cast<int64_t>(mine) < a.lvl_rows, 26, mine);
-      for (int j = 0; j < cnt; j += kMsCheckAhead) {
-        vid_t w[kMsCheckAhead];
-        int lw[kMsCheckAhead];
+    if (kCount || __ballot(ru && !is_src) != 0ull)
+      ms_walk_row<L, kMsWalkAhead>(lvl, g.col, rs, re, a.m.lvl_rows, 26, [&](int valid, const vid_t* w, const int* lw) {
 #pragma unroll
-        for (int i = 0; i < kMsCheckAhead; ++i) {
-          w[i] = static_cast<vid_t>(__builtin_amdgcn_readlane(static_cast<int>(mine), min(j + i, cnt - 1)));
-          lw[i] = lvl[static_cast<int64_t>(w[i]) * kMsSources + lane];
-        }
-#pragma unroll
-        for (int i = 0; i < kMsCheckAhead; ++i) {
-          const bool valid = j + i < cnt;  // (wave-uniform)
+        for (int i = 0; i < kMsWalkAhead; ++i) {
+          // (&, not &&: a branch on the wave-uniform `in` would take the entry's level load along)
+          const bool in = i < valid;
           const bool rw = lw[i] != kNone;
           if (kCount) {
             const int d = lu - lw[i];
             if (kDirected) {
-              if (valid && on && rw && !ru) ++cross;
-              if (valid && ru && rw && d > 1) ++gap;
+              cross += in & on & rw & !ru;
+              gap += in & ru & rw & (d > 1);
             } else {
-              if (valid && on && ru != rw) ++cross;
-              if (valid && ru && rw && (d > 1 || d < -1)) ++gap;
+              cross += in & on & (ru != rw);
+              gap += in & ru & rw & ((d > 1) | (d < -1));
             }
           }
-          if (valid && ru && rw && lw[i] + 1 == lu && !has_par) {
-            has_par = true;
-            par = w[i];
-          }
+          const bool found = in & ru & rw & (lw[i] + 1 == lu) & !has_par;
+          par = found ? w[i] : par;
+          has_par |= found;
         }
-        if (!kCount && __ballot(ru && !is_src && !has_par) == 0ull) {
-          walk = false;
-          break;
-        }
-      }
-    }
+        return kCount || __ballot(ru && !is_src && !has_par) != 0ull;
+      });
     if (kCount && (is_src ? lu != 0 : (ru && !has_par))) ++orphan;
     if (kParent && on) a.par[r * kMsSources + lane] = is_src ? static_cast<uint32_t>(u) : par;
   }
@@ -534,31 +512,26 @@ void ms_check_launch(const MsCheckArgs& a, hipStream_t st) {
 
 void ms_check(const MsCheckArgs& a, hipStream_t st) {
   if (a.g.rows <= 0 || (!a.out && !a.par)) return;
-  if (a.directed) {
-    if (a.lvl_bytes == 2) ms_check_launch<uint16_t, true>(a, st);
-    else ms_check_launch<uint8_t, true>(a, st);
-  } else {
-    if (a.lvl_bytes == 2) ms_check_launch<uint16_t, false>(a, st);
-    else ms_check_launch<uint8_t, false>(a, st);
-  }
+  ms_level_type(a.m.lvl_bytes, [&](auto l) {
+    using L = decltype(l);
+    if (a.directed) ms_check_launch<L, true>(a, st);
+    else ms_check_launch<L, false>(a, st);
+  });
 }
 
 unsigned long long take_check_ms() { return take_check_local(); }
 
 void ms_init(const MsInitArgs& a, hipStream_t st) {
-  if (a.s.lvl_bytes == 2) ms_init_kernel<uint16_t><<<1, kWave, 0, st>>>(a);
-  else ms_init_kernel<uint8_t><<<1, kWave, 0, st>>>(a);
+  ms_level_type(a.s.lvl_bytes, [&](auto l) { ms_init_kernel<decltype(l)><<<1, kWave, 0, st>>>(a); });
 }
 
 void ms_pull(const MsPullArgs& a, hipStream_t st) {
   const unsigned grid = grid_for(a.s.g.rows, kMsBlock, kMsMaxGrid);
-  if (a.s.directed) {
-    if (a.s.lvl_bytes == 2) ms_pull_kernel<uint16_t, true><<<grid, kMsBlock, 0, st>>>(a);
-    else ms_pull_kernel<uint8_t, true><<<grid, kMsBlock, 0, st>>>(a);
-  } else {
-    if (a.s.lvl_bytes == 2) ms_pull_kernel<uint16_t, false><<<grid, kMsBlock, 0, st>>>(a);
-    else ms_pull_kernel<uint8_t, false><<<grid, kMsBlock, 0, st>>>(a);
-  }
+  ms_level_type(a.s.lvl_bytes, [&](auto l) {
+    using L = decltype(l);
+    if (a.s.directed) ms_pull_kernel<L, true><<<grid, kMsBlock, 0, st>>>(a);
+    else ms_pull_kernel<L, false><<<grid, kMsBlock, 0, st>>>(a);
+  });
 }
 
 void ms_push(const MsPushArgs& a, hipStream_t st) {
@@ -572,8 +545,7 @@ void ms_push(const MsPushArgs& a, hipStream_t st) {
 
 void ms_settle(const MsSettleArgs& a, hipStream_t st) {
   const unsigned grid = grid_for(a.max_touched, kMsBlock, kMsMaxGrid);
-  if (a.s.lvl_bytes == 2) ms_settle_kernel<uint16_t><<<grid, kMsBlock, 0, st>>>(a);
-  else ms_settle_kernel<uint8_t><<<grid, kMsBlock, 0, st>>>(a);
+  ms_level_type(a.s.lvl_bytes, [&](auto l) { ms_settle_kernel<decltype(l)><<<grid, kMsBlock, 0, st>>>(a); });
 }
 
 void ms_degree_sums(const MsDegreeArgs& a, hipStream_t st) {

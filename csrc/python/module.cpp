@@ -794,11 +794,17 @@ PYBIND11_MODULE(_dbfs_native, m) {
           "run_batch",
           [](Engine& e, const std::vector<int64_t>& sources, const std::string& direction, bool levels, bool validate,
              bool parents, bool betweenness, bool path_counts) {
-            const BatchDirection d = parse_batch_direction(direction);
+            BatchOptions o;
+            o.direction = parse_batch_direction(direction);
+            o.keep_levels = levels;
+            o.validate = validate;
+            o.keep_parents = parents;
+            o.betweenness = betweenness;
+            o.keep_path_counts = path_counts;
             BatchResult r;
             {
               py::gil_scoped_release rel;
-              r = e.run_batch(sources, d, levels, validate, parents, betweenness, path_counts);
+              r = e.run_batch(sources, o);
             }
             return r;
           },

@@ -49,6 +49,36 @@ def _path():
     return _csr(300, np.arange(0, 299), np.arange(1, 300))
 
 
+FAN_SIZES = (1, 7, 8, 9, 63, 64, 65, 71, 72, 73, 128, 129)
+FAN_MIDS = 129
+
+
+def fan_vertex(d):
+    """The vertex of the fans graphs whose row is exactly the first d mids."""
+    return 1 + FAN_MIDS + FAN_SIZES.index(d)
+
+
+def _fans(path):
+    """Rows built around the row walk's boundaries (64 column ids per step, 8
+    level lines per group): source 0, 129 mids (1 .. 129) adjacent to it, and
+    for every d of FAN_SIZES one fan vertex adjacent to exactly the first d
+    mids -- a row of d entries, all predecessors with one shortest path each,
+    so the source's path count there is d.  path > 0: that many vertices in a
+    row hang off the source (300: the pass reruns with 16-bit levels)."""
+    def build():
+        u = [np.zeros(FAN_MIDS, dtype=np.int64)]
+        v = [np.arange(1, FAN_MIDS + 1)]
+        for d in FAN_SIZES:
+            u.append(np.full(d, fan_vertex(d)))
+            v.append(np.arange(1, d + 1))
+        n = 1 + FAN_MIDS + len(FAN_SIZES)
+        if path:
+            u.append(np.concatenate([[0], np.arange(n, n + path - 1)]))
+            v.append(np.arange(n, n + path))
+        return _csr(n + path, np.concatenate(u), np.concatenate(v))
+    return build
+
+
 # name -> builder of a HostCSR, or a file path (read by the BFS itself)
 GRAPHS = {
     "rmat10": _rmat(10),
@@ -57,6 +87,8 @@ GRAPHS = {
     "star5000": _star,
     "two_components": _two_components,
     "path300": _path,
+    "fans": _fans(0),
+    "fans300": _fans(300),
     "file_two_components": os.path.join(DATA, "two_components.txt"),
     "file_chain8": os.path.join(DATA, "chain8.txt"),
 }
@@ -106,6 +138,8 @@ def sources(name, kind):
         special = [0, 17, n - 1]  # the centre, a leaf, the tail's end
     elif name == "path300":
         special = [0, n - 1, 150]
+    elif name in ("fans", "fans300"):
+        special = [0, fan_vertex(129), 1, n - 1]  # the source of the d paths, the longest fan, a mid, the path's end
     elif name in ("two_components", "file_two_components"):
         special = [0, n - 1]  # one source in each component
     if k > 1:

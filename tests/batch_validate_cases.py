@@ -21,6 +21,9 @@ CASES = [
     ("two_components", "k64"),
     ("path300", "k64"),
     ("file_chain8", "k1"),
+    ("fans300", "k1"),
+    ("fans300", "k64"),
+    ("fans", "k64"),
 ]
 _edge_codes = {}
 _reference = {}
@@ -81,12 +84,13 @@ def positive(bfs, name, kind, direction):
     levels = bfs.batch_levels()
     bc.check_batch(name, src, res, levels)
     check_clean(name, kind, src, res, levels, bfs.batch_parents())
-    assert res.wide_levels == (name == "path300")
+    assert res.wide_levels == (name in ("path300", "fans300"))
 
 
 # parents without validate: the parent form alone, which leaves a row once every reached lane has
 # its parent -- the 5000-entry row, the 16-bit form, skewed rows with k < 64, three passes with masked lanes
-PARENTS_ONLY_CASES = [("star5000", "k64"), ("path300", "k64"), ("rmat13", "k63"), ("n4097", "k130")]
+PARENTS_ONLY_CASES = [("star5000", "k64"), ("path300", "k64"), ("rmat13", "k63"), ("n4097", "k130"),
+                      ("fans300", "k1"), ("fans300", "k64"), ("fans", "k64")]
 
 
 def parents_only(bfs, name, kind):

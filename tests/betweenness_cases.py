@@ -28,7 +28,11 @@ RTOL = 1e-9
 
 # (graph, source set): undirected from batch_cases, directed from directed_cases
 UNDIRECTED = [("star5000", "k64"), ("n4097", "k130"), ("rmat13", "k63"), ("rmat13", "k64dup"), ("rmat10", "all"),
-              ("two_components", "k64"), ("path300", "k64"), ("file_chain8", "k1")]
+              ("two_components", "k64"), ("path300", "k64"), ("file_chain8", "k1"),
+              ("fans300", "k1"), ("fans300", "k64"), ("fans", "k64")]
+# exact path counts (path_counts): the fans graphs' rows end on every boundary of the row walk
+PATH_COUNT_CASES = [("rmat10", "k64dup", False), ("d_rmat10", "k64", True),
+                    ("fans300", "k1", False), ("fans300", "k64", False), ("fans", "k64", False)]
 DIRECTED = [("d_rmat13", "k64dup"), ("star_in5000", "k64"), ("star_out5000", "k64"), ("one_way_bridge", "k64"),
             ("tiny5", "k64"), ("empty3", "k64")]
 CASES = [(g, k, False) for g, k in UNDIRECTED] + [(g, k, True) for g, k in DIRECTED]
@@ -97,7 +101,7 @@ def matches_oracle(rt, name, kind, directed, **kw):
     launches = sum(2 * (int(depth[p:p + 64].max()) - 1) for p in range(0, len(src), 64))
     assert res.bc_launches == launches
     assert 0 <= res.bc_rows_walked <= launches * n
-    assert res.wide_levels == (name in ("path300", "d_path300"))
+    assert res.wide_levels == (name in ("path300", "d_path300", "fans300"))
     return res
 
 
@@ -159,7 +163,19 @@ def hand_doubled_square(rt):
     assert list(dbfs.cpu_betweenness(csr, [0, 1, 2, 3], False, True)[1][0]) == [1.0, 2.0, 3.0, 1.0]
 
 
-HAND = {"path300": hand_path300, "d_path300": hand_d_path300, "back_edge10": hand_back_edge10,
+def hand_fans300(rt):
+    """From source 0 every fan vertex has one shortest path per entry of its row."""
+    csr = bc.host_csr("fans300")
+    bfs = dbfs.BFS(csr, rt)
+    bfs.run_batch([0], path_counts=True)
+    got = bfs.batch_path_counts()[0]
+    ref = dbfs.cpu_betweenness(csr, [0], False, True)[1][0]
+    for d in bc.FAN_SIZES:
+        assert got[bc.fan_vertex(d)] == d and ref[bc.fan_vertex(d)] == d
+    assert np.array_equal(got, ref)
+
+
+HAND = {"path300": hand_path300, "fans300": hand_fans300, "d_path300": hand_d_path300, "back_edge10": hand_back_edge10,
         "doubled_square": hand_doubled_square}
 
 

@@ -40,7 +40,7 @@ def test_batch_matches_oracle(graph, kind, direction):
     if direction == "alternate":
         assert all(l[2] == ("P" if l[1] % 2 == 0 else "L") for l in res.levels)
     # depth 299 does not fit one-byte levels: the pass was rerun with 16-bit ones
-    assert res.wide_levels == (graph == "path300")
+    assert res.wide_levels == (graph in ("path300", "fans300"))
 
 
 def test_auto_takes_both_forms():

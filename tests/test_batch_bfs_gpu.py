@@ -42,7 +42,7 @@ def test_batch_matches_oracle_gpu(gpu_runtime, graph, kind, direction):
         assert set(bc.forms(res)) <= {forced}
     if direction == "alternate":
         assert all(l[2] == ("P" if l[1] % 2 == 0 else "L") for l in res.levels)
-    assert res.wide_levels == (graph == "path300")
+    assert res.wide_levels == (graph in ("path300", "fans300"))
 
 
 def test_auto_takes_both_forms_gpu(gpu_runtime):

@@ -8,6 +8,8 @@ the kernel; the checks themselves are in batch_validate_cases.py.
   two_components k64  lanes for which half the graph is unreached: no cross edges between components
   path300 k64         16-bit levels after the rerun
   file_chain8 k1      one lane
+  fans300 k1, k64     rows of 1, 7, 8, 9, 63, 64, 65, 71, 72, 73, 128 and 129 entries, 16-bit levels
+  fans k64            the same rows, one-byte levels
 """
 import os
 

@@ -12,6 +12,10 @@ batch_validate_cases.py, the same as on the CPU backend.
   two_components k64  lanes for which half the graph is unreached: no cross edges between components
   path300 k64         16-bit levels, the uint16_t instantiation, after the rerun
   file_chain8 k1      one lane
+  fans300 k1, k64     rows of 1, 7, 8, 9, 63, 64, 65, 71, 72, 73, 128 and 129 entries: every boundary
+                      of the row walk (64 column ids per step, 8 level lines per group, the last
+                      group's repeated line); 16-bit levels
+  fans k64            the same rows, one-byte levels
 """
 import os
 

@@ -41,7 +41,7 @@ def test_betweenness_matches_oracle(rt, graph, kind, directed):
     bt.matches_oracle(rt, graph, kind, directed)
 
 
-@pytest.mark.parametrize("graph,kind,directed", [("rmat10", "k64dup", False), ("d_rmat10", "k64", True)])
+@pytest.mark.parametrize("graph,kind,directed", bt.PATH_COUNT_CASES)
 def test_path_counts_equal_oracle(rt, graph, kind, directed):
     bt.path_counts(rt, graph, kind, directed)
 

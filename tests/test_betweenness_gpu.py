@@ -39,7 +39,7 @@ def test_betweenness_matches_oracle_gpu(gpu_runtime, graph, kind, directed):
     bt.matches_oracle(gpu_runtime, graph, kind, directed)
 
 
-@pytest.mark.parametrize("graph,kind,directed", [("rmat10", "k64dup", False), ("d_rmat10", "k64", True)])
+@pytest.mark.parametrize("graph,kind,directed", bt.PATH_COUNT_CASES)
 def test_path_counts_equal_oracle_gpu(gpu_runtime, graph, kind, directed):
     bt.path_counts(gpu_runtime, graph, kind, directed)
 
