@@ -5,6 +5,7 @@
 // collectives are exercised by the CPU test-suite exactly as they run on the
 // GPU.  Not a performance path.
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -375,7 +376,9 @@ class CpuBackend final : public Backend {
       for (int s = 0; s < a.m.k; ++s) {
         if (level_at(a.m, a.g.lo + r, s) != a.level) continue;
         any = true;
-        a.own[r * kMsSources + s] = bc_row_sum(a, r, s, a.level - 1);
+        const double sum = bc_row_sum(a, r, s, a.level - 1);
+        a.own[r * kMsSources + s] = sum;
+        if (!(sum <= DBL_MAX)) *a.overflow |= 1ull << s;  // (out of double's range: the engine fails the batch)
       }
       if (any && a.walked) ++*a.walked;
     }

@@ -456,7 +456,7 @@ void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bo
   if (b.bc_val.size() == 0) {
     b.bc_val = DBuf<double>(be_, own_vals * P);
     if (P > 1) b.bc_own = DBuf<double>(be_, own_vals);
-    b.bc_walked = DBuf<unsigned long long>(be_, 1);
+    b.bc_walked = DBuf<unsigned long long>(be_, 2);  // (rows walked; MsBcArgs::overflow)
   }
   be_.memset_async(b.bc_walked.data(), 0, b.bc_walked.bytes());
   MsBcArgs a;
@@ -466,6 +466,7 @@ void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bo
   a.own = P > 1 ? b.bc_own.data() : b.bc_val.data();
   a.dep = accumulate ? b.bc_dep.data() : nullptr;
   a.walked = b.bc_walked.data();
+  a.overflow = b.bc_walked.data() + 1;
   // the long rows of a view, listed once per engine and threshold
   auto long_rows = [&](int which, const ShardView& view) {
     a.long_rows = nullptr;
@@ -507,6 +508,15 @@ void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bo
     ++out.bc_launches;
   }
   if (fault_.kind == "bc_device" && fault_.rank == comm_.rank()) be_.inject_device_check();
+  // A count past DBL_MAX is inf, and the backward sweep's inf * 0 would be
+  // NaN: the batch fails here, on every rank, before a count is copied out.
+  unsigned long long over = 0;
+  be_.to_host(&over, a.overflow, sizeof(over));
+  if (P > 1)
+    for (int64_t x : comm_.allgather_host_i64(static_cast<int64_t>(over))) over |= static_cast<unsigned long long>(x);
+  if (over != 0ull)
+    throw Error("run_batch: the shortest-path counts from source " + std::to_string(m.src[__builtin_ctzll(over)]) +
+                " exceed the range of a double; betweenness and path counts are not available for this graph");
   if (counts)
     copy_transposed(be_, b.bc_val.data(), n, m.k, kept_.counts.data() + static_cast<size_t>(first) * static_cast<size_t>(n),
                     static_cast<size_t>(n), [](double x) { return x; });

@@ -5,6 +5,8 @@
 // stable two-pass counting sort instead of vector<vector<int>>.
 // cpu_bfs is the oracle of bfs.cu:923-945 (std::queue BFS).
 #include <algorithm>
+#include <cfloat>
+#include <string>
 #include <vector>
 
 #include "dbfs/graph.hpp"
@@ -86,6 +88,11 @@ CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t
   std::vector<double> sigma(n), delta(n);
   std::vector<vid_t> order;  // the queue; read backwards it is Brandes' stack
   order.reserve(n);
+  // (a count past DBL_MAX is inf, and the dependencies above it NaN: as Engine::run_batch, an error)
+  auto over = [](int64_t src) {
+    return "cpu_betweenness: the shortest-path counts from source " + std::to_string(src) +
+           " exceed the range of a double; betweenness and path counts are not available for this graph";
+  };
   for (size_t i = 0; i < sources.size(); ++i) {
     const int64_t src = sources[i];
     DBFS_CHECK(src >= 0 && src < g.n, "source vertex out of range");
@@ -105,6 +112,7 @@ CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t
         for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e)
           if (dist[g.col[e]] == lu - 1) s += sigma[g.col[e]];
         sigma[u] = s;
+        DBFS_CHECK(s <= DBL_MAX, over(src));
       }
       for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e) {
         const vid_t w = g.col[e];
@@ -113,7 +121,10 @@ CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t
           order.push_back(w);
         }
         // (u's count is final: every vertex one level closer was dequeued before it)
-        if (directed && dist[w] == lu + 1) sigma[w] += sigma[u];
+        if (directed && dist[w] == lu + 1) {
+          sigma[w] += sigma[u];
+          DBFS_CHECK(sigma[w] <= DBL_MAX, over(src));
+        }
       }
     }
     for (size_t at = order.size(); at-- > 0;) {

@@ -1213,6 +1213,12 @@ struct MsBcArgs {
   int level = 0;
   bool leaf = false;
   unsigned long long* walked = nullptr;
+  // Forward: bit s is set (an integer atomic OR) when a count stored for
+  // source s is not finite -- more than DBL_MAX shortest paths.  The engine
+  // reads it after the forward sweep and fails the batch: the backward sweep
+  // never sees such a count (with every sigma finite, delta <= n and every
+  // coefficient are finite, so it needs no test of its own).
+  unsigned long long* overflow = nullptr;
   // Long rows (HIP; optional): the n_long owned rows of more than split_above
   // entries in (row_off, col), in any order (Backend::ms_bc_long_rows).  They
   // are walked by a launch of their own, a workgroup of 16 waves per row, each

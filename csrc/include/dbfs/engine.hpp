@@ -560,6 +560,10 @@ class Engine {
   // bytes on the host).  Both need keep_levels; BatchResult::bc_ms.  Several
   // ranks: the simple form -- the value matrix is replicated and the owned
   // lines are all-gathered after every launch.
+  // Path counts are doubles: a batch in which a source has more than DBL_MAX
+  // (~2^1024) shortest paths to some vertex throws after that pass's forward
+  // sweep, on every rank, naming the first such source, and leaves no result
+  // (extended-range counts: not implemented).
   BatchResult run_batch(const std::vector<int64_t>& sources, const BatchOptions& o = {});
   // The last batch's dependency sums, one per vertex: dep(v) = the sum over the
   // source slots i with v != src_i of delta_{src_i}(v) -- raw: not halved on
@@ -726,7 +730,8 @@ class Engine {
     DBuf<uint32_t> par;    // MsCheckArgs::par (allocated by the first batch that keeps parents)
     // MsBcArgs (allocated by the first batch that asks for betweenness or path
     // counts): the value matrix, several ranks' owned lines, the dependency
-    // sums of the owned rows, the rows-walked counter
+    // sums of the owned rows, the rows-walked counter followed by the overflow
+    // mask (MsBcArgs::walked, ::overflow)
     DBuf<double> bc_val, bc_own, bc_dep;
     DBuf<unsigned long long> bc_walked;
     // MsBcArgs::long_rows of the predecessor rows [0] and the out-rows [1]

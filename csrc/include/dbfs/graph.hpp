@@ -100,7 +100,8 @@ CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src);
 // slots i with v != sources[i] of delta_{sources[i]}(v): raw, not halved, not
 // rescaled.  directed: g holds out-entries only (the entries into v are found
 // from their tails' rows); otherwise g is symmetric and v's own row lists them.
-// sigma (want_counts): [k][n] row-major, 0 where unreached.
+// sigma (want_counts): [k][n] row-major, 0 where unreached.  Throws, naming
+// the source, when a count exceeds DBL_MAX (as Engine::run_batch does).
 struct CpuBetweennessResult {
   std::vector<double> dep;
   std::vector<double> sigma;

@@ -15,7 +15,11 @@
 // matches, and a vertex none of whose lanes sits on the launch's level is
 // skipped after its own level line, before its row offsets are read.
 // Every sum is pull-form and per lane in stored row order: no atomics on
-// floating-point values, the same bits on every run.
+// floating-point values, the same bits on every run.  A forward count past
+// DBL_MAX sets its source's bit in MsBcArgs::overflow (an integer OR) and the
+// engine fails the batch before the backward sweep.
+#include <cfloat>
+
 #include "ms_walk.hpp"
 
 namespace dbfs {
@@ -69,8 +73,13 @@ __device__ __forceinline__ double ms_bc_row_sum(const MsBcArgs& a, const L* __re
 }
 
 // A vertex's forward result: the path counts of the lanes on the level.
-__device__ __forceinline__ void ms_bc_store_forward(const MsBcArgs& a, int64_t r, bool at, double sum) {
+// Returns the lanes whose count left double's range, for MsBcArgs::overflow
+// (the engine fails the batch on it).  The caller ORs them in a scalar and
+// stores once, after its rows: an atomic inside the row loop would turn the
+// loop's scalar row-offset loads into vector loads.  Wave-uniform call.
+__device__ __forceinline__ unsigned long long ms_bc_store_forward(const MsBcArgs& a, int64_t r, bool at, double sum) {
   if (at) a.own[r * kMsSources + lane_id()] = sum;
+  return __ballot(at && !(sum <= DBL_MAX));
 }
 
 // A vertex's backward result from acc, the sum of its successors'
@@ -96,7 +105,7 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_forward_kernel(MsBcArgs a) {
   const int lane = lane_id();
   const bool on = (a.m.batch_mask >> lane) & 1ull;  // lanes past the pass's sources are idle
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-  unsigned long long walked = 0;
+  unsigned long long walked = 0, over = 0;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
   for (int64_t r = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + wave; r < g.rows; r += stride) {
     const int64_t v = g.lo + r;
@@ -107,9 +116,10 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_forward_kernel(MsBcArgs a) {
     DBFS_DCHECK(rs >= 0 && rs <= re && re <= a.nnz, 29, r);
     if (a.n_long > 0 && re - rs > a.split_above) continue;  // (ms_bc_long_kernel's)
     ++walked;
-    ms_bc_store_forward(a, r, at, ms_bc_row_sum<L>(a, lvl, rs, re, at, a.level - 1));
+    over |= ms_bc_store_forward(a, r, at, ms_bc_row_sum<L>(a, lvl, rs, re, at, a.level - 1));
   }
   if (a.walked && lane == 0 && walked) atomicAdd(a.walked, walked);
+  if (lane == 0 && over) atomicOr(a.overflow, over);
 }
 
 template <class L>
@@ -157,7 +167,7 @@ __global__ __launch_bounds__(kMsBcLongBlock) void ms_bc_long_kernel(MsBcArgs a) 
   const bool on = (a.m.batch_mask >> lane) & 1ull;
   const int64_t my_src = on ? a.m.src[lane] : -1;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-  unsigned long long walked = 0;
+  unsigned long long walked = 0, over = 0;  // (wave 0's)
   for (int64_t i = blockIdx.x; i < a.n_long; i += gridDim.x) {
     const int64_t r = a.long_rows[i];
     const int64_t v = g.lo + r;
@@ -177,11 +187,12 @@ __global__ __launch_bounds__(kMsBcLongBlock) void ms_bc_long_kernel(MsBcArgs a) 
       for (int w = 0; w < kMsBcLongWaves; ++w) sum += s_part[w][lane];
       ++walked;
       if (kBackward) ms_bc_store_backward(a, r, at, at && v != my_src, sum);
-      else ms_bc_store_forward(a, r, at, sum);
+      else over |= ms_bc_store_forward(a, r, at, sum);
     }
     __syncthreads();  // (s_part is the next row's)
   }
   if (a.walked && threadIdx.x == 0 && walked) atomicAdd(a.walked, walked);
+  if (!kBackward && threadIdx.x == 0 && over) atomicOr(a.overflow, over);
 }
 
 __global__ __launch_bounds__(kMsBcBlock) void ms_bc_long_rows_kernel(const eid_t* row_off, int64_t rows, int64_t above,
@@ -216,7 +227,10 @@ void ms_bc_init(const MsBcArgs& a, hipStream_t st) {
   ms_bc_init_kernel<<<grid_for(a.m.lvl_rows, kMsBcBlock / kWave, kMsBcGrid), kMsBcBlock, 0, st>>>(a);
 }
 
-void ms_bc_forward(const MsBcArgs& a, hipStream_t st) { ms_bc_sweep<false>(a, st); }
+void ms_bc_forward(const MsBcArgs& a, hipStream_t st) {
+  DBFS_CHECK(a.overflow, "ms_bc_forward: MsBcArgs::overflow missing");
+  ms_bc_sweep<false>(a, st);
+}
 void ms_bc_backward(const MsBcArgs& a, hipStream_t st) { ms_bc_sweep<true>(a, st); }
 
 void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,

@@ -237,7 +237,10 @@ class BFS:
         ``path_counts=True`` keeps the path counts for batch_path_counts().
         Both read the level matrix (``levels=True``) and are timed on their
         own: ``BatchResult.bc_ms``.  512 + 8 bytes per owned vertex on the
-        device.  Several ranks use a simple replicated form: correct, not fast."""
+        device.  Several ranks use a simple replicated form: correct, not fast.
+        The counts are doubles: when a source has more than 2**1024 shortest
+        paths to some vertex the call raises (on every rank, naming the source)
+        and leaves no result; it never returns a non-finite value."""
         if direction not in BATCH_DIRECTIONS:
             raise ValueError(f"direction must be one of {BATCH_DIRECTIONS}")
         if (validate or parents) and not levels:
@@ -262,7 +265,8 @@ class BFS:
         """Shortest-path counts of the last run_batch(path_counts=True) as
         float64 [k, n]: row i holds the number of shortest paths from
         sources[i] to every vertex (1 for the source itself, 0 where it does
-        not reach), exact while below 2**53.  k x n x 8 bytes on the host."""
+        not reach), exact while below 2**53, rounded above (run_batch raises
+        where one would pass 2**1024).  k x n x 8 bytes on the host."""
         return self.engine.gather_batch_path_counts()
 
     def batch_levels(self) -> np.ndarray:

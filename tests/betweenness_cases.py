@@ -10,7 +10,9 @@ multiplies or divides non-negative doubles, so nothing cancels: a result's
 relative error is at most (roundings on its dependency chain) x 2^-53, and the
 chain is shorter than 8 (nnz + n) ~ 2.2e6 on the largest graph here (rmat13,
 262144 entries): 2.4e-10 per side.  Path counts are compared for equality:
-sums of integers below 2^53 are exact in any order."""
+sums of integers below 2^53 are exact in any order.  Counts at and above 2^53,
+up to the range contract at 2^1024, are betweenness_exact_cases.py's, against
+an exact reference."""
 import json
 import os
 import subprocess
