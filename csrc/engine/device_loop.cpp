@@ -3,13 +3,19 @@
 // decides each level's direction itself (LevelCtrl) and stamps a mapped
 // mailbox the host spins on.  Split into
 //   * the planner: direction / frontier prediction (Beamer through the shared
-//     level_ctrl_finish), the chain form of a top-down level (td_form) and
-//     whether an enqueued chain is live for the level it turned out to be;
+//     level_ctrl_finish); plan_level, which decides everything about a level's
+//     chain -- its form and every variant of it -- as a value (LevelPlan)
+//     before anything is launched; and whether an enqueued chain is live for
+//     the level it turned out to be;
 //   * the chain emitters, one per form: 'S' sparse top-down (emit_sparse),
 //     'X' binned top-down (emit_binned), 'T' dense top-down (emit_dense),
-//     'B' bottom-up (emit_bottom_up); with several ranks each chain also
-//     enqueues its collectives and its level end (Comm::level_end, or the
-//     direct exchanges the kernels run themselves).
+//     'B' bottom-up (emit_bottom_up): each fills argument blocks from the
+//     plan and launches; with several ranks each chain also enqueues its
+//     collectives and its level end (Comm::level_end, or the direct exchanges
+//     the kernels run themselves).  An emitter decides nothing but what only
+//     the transport can answer when asked (direct lists, a direct level end, a
+//     pushed frontier table): the plan holds the request, the Chain the
+//     outcome.
 // The reference's host loop (bfs.cu:569-620, bfs_mpi.cu:581-632) launches,
 // synchronises, copies and reads managed counters once per level.
 #include <algorithm>
@@ -18,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "dbfs/engine.hpp"
@@ -34,18 +41,52 @@ class DeviceLoop {
   RunResult run();
 
  private:
-  // One enqueued level chain.
-  struct Chain {
-    int L = 0;
-    char d = 'T';       // form: 'T', 'S', 'X', 'B'
-    char pf = 'I';      // the previous level's form ('I': the seed)
+  // Everything decided about one level's chain before anything is launched
+  // (trivially copyable: planning allocates nothing).
+  struct LevelPlan {
+    int level = 0;
+    char dir = 'T';     // 'T' or 'B'
+    char form = 'T';    // 'T', 'S', 'X', 'B'
     int64_t cap = 0;    // sparse: the global frontier edges it stays live for
+    bool gather = false;  // several ranks: its collective also all-gathers its output frontier
+    char pf = 'I';      // the previous level's form ('I': the seed)
+    bool in_gathered = false;  // the input frontier is global already
+    int cur = 0;        // input frontier buffer (level L reads frontier_[(L + 1) & 1])
+    // the level's predicted (or, re-enqueued, actual) frontier edges, the
+    // visited degree sum and the reached vertices with an edge at its start
+    // (each < 0: unknown)
+    double mf_hint = -1, vis_hint = -1, reach_hint = -1;
+    // dense ('T'; listed: 'X' too) -- listed: a sparse level (or the seed)
+    // handed over the work list, no compaction; the unvisited filter; the
+    // hubs' visited bits staged in LDS; direct: byte-map levels write the
+    // level itself, and (hub_marks) unvisited hubs are claimed by marks; the
+    // level run in `parts` parts
+    bool listed = false, unvis = false, hub_filter = false, direct = false, hub_marks = false;
+    int parts = 1;
+    // sparse ('S') -- compacted: the work list comes from a compaction (or the
+    // bitmap), not handed over; from_bits: the kernel reads the bottom-up
+    // output bitmap itself; several ranks: the owners' side's workgroups, and
+    // (fuse_ok) a tiny level's owner side and level end in td_sparse's last
+    // workgroup
+    bool compacted = false, from_bits = false, fuse_ok = false;
+    int64_t apply_grid = 1;
+    // bottom-up ('B') -- follow_up: the previous level was bottom-up too; cut:
+    // the hub cut's launches, xcut: with the remote claims' all-to-all
+    int whole_units = 0;
+    bool follow_up = false, cut = false, xcut = false;
+    // several ranks: the level end may run in the chain's last kernel, and the
+    // output frontier is asked to be pushed by the producing kernel
+    bool end_ok = false, want_push = false;
+  };
+
+  static_assert(std::is_trivially_copyable<LevelPlan>::value, "a plan is copied per level, never allocated");
+
+  // One enqueued level chain: its plan, and what only emission can know.
+  struct Chain {
+    LevelPlan p;
     // what every kernel of the chain tests at entry: {ctrl, the level's
     // enqueued direction, cap}, built once in enqueue_level
     ChainGuard guard;
-    double mf_hint = -1;
-    int cur = 0;        // input frontier buffer (level L reads frontier_[(L + 1) & 1])
-    bool in_gathered = false;  // the input frontier is global already
     bool fused_scan = false;   // the chain's last kernel finishes the level
     bool level_ended = false;  // ... and also ran its level end (direct exchange)
     bool folded = false;       // ... and also scanned its unit prefixes (UpdateArgs::fold_scan)
@@ -75,8 +116,10 @@ class DeviceLoop {
   int64_t sparse_cap_ = 0;
   int64_t list_max_ = 0, xsparse_lim_ = 0, fuse_cap_ = 0;
   bool lists_unlimited_ = false, counted_ = false;
-  double vis_hint_ = -1.0;  // the next enqueued level's visited degree sum at its start (< 0 unknown)
-  double reach_hint_ = -1.0;  // ... and its reached vertices with an edge (< 0 unknown)
+  int coresident_ = 1;         // Comm::coresident, Comm::split_waits: constant for a run
+  bool split_waits_ = false;
+  bool cells_fit_ = false;     // a direct level end's cells carry < 2^32 new vertices and < 2^40 degrees per rank
+  bool cut_shard_ok_ = false;  // the shard has what a hub-cut level reads
   int bin_shift_ = 12;
   int64_t nbins_ = 0;
   bool binned_ = false;
@@ -87,11 +130,18 @@ class DeviceLoop {
   LevelCtrl init_;
   UpdateArgs ua_;  // the update's fields common to every chain
 
-  // ---- per-level records of what was enqueued ----
-  std::vector<char> enq_dir_, enq_form_, enq_gather_, enq_fused_;
-  std::vector<const FrontierTable*> enq_push_;  // level L's output pushed (Chain::push)
-  std::vector<int64_t> enq_cap_;
-  std::vector<std::pair<int, int>> evs_;
+  // ---- per level: the latest chain enqueued for it ----
+  std::vector<LevelPlan> plans_;
+  // ... and what its emission left for later: the next level's compaction
+  // still owes its unit prefixes (a fused finish only did the totals), the
+  // output frontier's pushed table (Chain::push), its phase-timing events
+  struct Emitted {
+    bool scan_owed = false;
+    const FrontierTable* push = nullptr;
+    std::pair<int, int> ev{-1, -1};
+  };
+  std::vector<Emitted> emitted_;
+  int first_bu_ = -1;  // the first level whose latest chain is bottom-up (-1: none yet)
   RunResult res_;
 
   // ---- host timing (DBFS_HOST_TIMING=1: enqueue / stamp-wait timeline to stderr) ----
@@ -129,8 +179,23 @@ class DeviceLoop {
     if (L & 1) return {e_.qscan2_.data(), e_.qbase2_.data(), e_.blk_vstart2_.data(), e_.qv_[1].data()};
     return {e_.qscan_.data(), e_.qbase_.data(), e_.blk_vstart_.data(), e_.qv_[0].data()};
   }
-  uint32_t* group_tickets();
-  bool cells_fit() const { return e_.g_.rows() < (int64_t(1) << 32) && e_.g_.nnz() < (int64_t(1) << 40); }
+  // A scratch buffer of the engine's, allocated on first use: n elements,
+  // zeroed then if asked (its users keep it zero between launches).
+  template <class T>
+  T* scratch(DBuf<T>& buf, size_t n, bool zero) {
+    if (!buf.data()) {
+      buf = DBuf<T>(be_, n);
+      if (zero) be_.memset_async(buf.data(), 0, buf.bytes());
+    }
+    return buf.data();
+  }
+  // two-level tickets (fused update finish, sparse levels read from a bitmap):
+  // zero between launches, each user re-zeroes what it took
+  uint32_t* group_tickets() {
+    return scratch(e_.td_group_ticket_, static_cast<size_t>(kFusedGroups * kBuQueueStride), true);
+  }
+  // the global byte map (zero between its users: every pack clears what it read)
+  uint8_t* byte_map() { return scratch(e_.next_bytes_, static_cast<size_t>(GW_) * kWordBits, true); }
   const volatile LevelMailbox* wait_stamp(int lv);
   LevelStamp stamp(int level, bool seed = false);
   LevelFinishArgs finish_args(int level, const ChainGuard& guard);
@@ -138,13 +203,13 @@ class DeviceLoop {
   ScanArgs scan_args(int level, const ChainGuard& guard);
 
   // ---- planner ----
-  char td_form(int L, double mf, int64_t* cap, bool exact) const;
+  LevelPlan plan_level(int L, char want, double mf, bool exact, bool gather, double vis, double reach) const;
   bool chain_valid(int L, char dir, int64_t mf) const;
   void predict(LevelCtrl& c, double nf, double mf, double pnf, double pmf, double reached, bool first, bool rising,
                double* enf, double* emf) const;
 
   // ---- emitters ----
-  void enqueue_level(int L, char d, int64_t cap, double mf_hint, bool gather);
+  void enqueue_level(const LevelPlan& p);
   void compact(const Chain& c, word_t* clear_all);
   void emit_sparse(Chain& c);
   void emit_binned(Chain& c);
@@ -181,16 +246,6 @@ void DeviceLoop::hmark(const std::string& what) {
   htl_.emplace_back(what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0_).count());
 }
 
-uint32_t* DeviceLoop::group_tickets() {
-  // two-level tickets (fused update finish, sparse levels read from a bitmap):
-  // zero between launches, each user re-zeroes what it took
-  if (!e_.td_group_ticket_.data()) {
-    e_.td_group_ticket_ = DBuf<uint32_t>(be_, static_cast<size_t>(kFusedGroups * kBuQueueStride));
-    be_.memset_async(e_.td_group_ticket_.data(), 0, e_.td_group_ticket_.bytes());
-  }
-  return e_.td_group_ticket_.data();
-}
-
 // Allocations, run constants, the once-per-graph degree moments.
 void DeviceLoop::setup() {
   e_.alloc_bitmap_state();
@@ -200,7 +255,7 @@ void DeviceLoop::setup() {
   P_ = part_.nranks;
   xc_ = e_.exchange();
   gv_ = e_.g_.view();
-  if (!e_.ctrl_.data()) e_.ctrl_ = DBuf<LevelCtrl>(be_, 1);
+  scratch(e_.ctrl_, 1, false);
   if (!e_.mailbox_host_) {
     void* dptr = nullptr;
     e_.mailbox_host_ = static_cast<LevelMailbox*>(be_.alloc_mapped(sizeof(LevelMailbox) * kMailboxSlots, &dptr));
@@ -210,10 +265,7 @@ void DeviceLoop::setup() {
   direct_ = !xc_ && e_.level_out(0).level8 && opt_.td_direct;
   byte_edges_ = direct_ ? opt_.td_direct_edges : opt_.td_byte_edges;
   bytes_ok_ = opt_.mode != Mode::BottomUp && byte_edges_ <= e_.total_directed_;
-  if (bytes_ok_ && !e_.next_bytes_.data()) {
-    e_.next_bytes_ = DBuf<uint8_t>(be_, static_cast<size_t>(GW_) * kWordBits);
-    be_.memset_async(e_.next_bytes_.data(), 0, e_.next_bytes_.bytes());
-  }
+  if (bytes_ok_) byte_map();
   // (several ranks too: remote claims travel as owner lists, td_sparse_apply
   // settles them on their owner)
   sparse_ = e_.sparse_enabled();
@@ -241,6 +293,14 @@ void DeviceLoop::setup() {
   lists_unlimited_ = list_max_ > 0 && list_max_ >= part_.part;
   xsparse_lim_ = std::min<int64_t>(opt_.xsparse_edges, list_max_);
   counted_ = comm_.counted_lists();
+  coresident_ = comm_.coresident();
+  split_waits_ = comm_.split_waits();
+  cells_fit_ = e_.g_.rows() < (int64_t(1) << 32) && e_.g_.nnz() < (int64_t(1) << 40);
+  // (several ranks: every condition the same on every rank -- the chain
+  // then carries the claims' collective)
+  cut_shard_ok_ = P_ == 1 ? gv_.hub_bits && gv_.nz_rec && gv_.unit_base && gv_.nz_pref && gv_.nz_row_off && gv_.head &&
+                                e_.zdeg_.data()
+                          : xc_ && P_ <= opt_.bu_cut_ranks && e_.g_.rec_all();
   // tiny sparse chains (several ranks, counted lists): live up to fuse_cap
   fuse_cap_ = xc_ && counted_ && opt_.xfuse_edges > 0 && 4 * opt_.xfuse_edges < list_max_ ? 4 * opt_.xfuse_edges : 0;
   if (list_max_ > 0 && e_.list_stride_ < list_max_ + 1) {
@@ -314,6 +374,11 @@ void DeviceLoop::setup() {
     mb->level = -2;
   }
   e_.rec_at(0);  // the first record segment, outside the timed window
+  // (no allocation per level in the timed window: an RMAT traversal has a
+  // dozen levels; a high-diameter one grows these geometrically)
+  plans_.reserve(64);
+  emitted_.reserve(64);
+  res_.chains.reserve(64);
 }
 
 // Wait until level `lv` (-1 = seed) has stamped its mailbox slot.
@@ -371,70 +436,200 @@ ScanArgs DeviceLoop::scan_args(int level, const ChainGuard& guard) {
 
 // ---- planner ------------------------------------------------------------------
 
-// Top-down form of level L whose frontier has (about) mf edges: sparse when
-// small (right after a bottom-up level too: the compaction then zeroes the
-// bottom-up input bitmap the sparse level writes into); *cap: the global
-// frontier edges a sparse chain stays live for.  (exact: mf is the level's
-// actual frontier edges -- a re-enqueue, which must be live.)
-char DeviceLoop::td_form(int L, double mf, int64_t* cap, bool exact) const {
-  *cap = 0;
-  if (xc_) {
-    if (list_max_ <= 0) return 'T';
-    if (counted_) {
-      // count-sized exchange: the largest lists cost nothing extra (cap 0:
-      // lists of a whole part, live for any level)
-      if (!exact && mf > static_cast<double>(xsparse_lim_)) return 'T';
-      if (exact && !lists_unlimited_ && mf > static_cast<double>(list_max_)) return 'T';
-      *cap = lists_unlimited_ ? 0 : list_max_;
+// The chain of level L, decided whole: `want` a bottom-up chain ('B'), the
+// top-down form its size calls for ('T'), or a dense top-down one whatever
+// its size ('D': the non-predicting loop's); mf: the level's
+// predicted (or, exact: its actual -- a re-enqueue, which must be live)
+// frontier edges, < 0 unknown; gather (several ranks): the chain's collective
+// also all-gathers its output frontier, for a bottom-up level predicted next;
+// vis / reach: the visited degree sum and the reached vertices with an edge at
+// the level's start (< 0 unknown).  Reads the run constants, the options and
+// the plans of earlier levels; launches, allocates and exchanges nothing.
+DeviceLoop::LevelPlan DeviceLoop::plan_level(int L, char want, double mf, bool exact, bool gather, double vis,
+                                             double reach) const {
+  LevelPlan p;
+  p.level = L;
+  // the previous level's form decides what hands this one its work list
+  p.pf = L == 0 ? 'I' : plans_[static_cast<size_t>(L - 1)].form;
+  // the input frontier is already global: all-gathered by the previous
+  // level's (or the seed's) collective
+  p.in_gathered = L == 0 ? seed_gather_ : plans_[static_cast<size_t>(L - 1)].gather;
+  p.cur = (L + 1) & 1;
+  p.gather = xc_ && gather;
+  p.mf_hint = mf;
+  p.vis_hint = vis;
+  p.reach_hint = reach;
+  const double total = static_cast<double>(e_.total_directed_);
+
+  // Top-down form of a level whose frontier has (about) fmf edges (unknown, as
+  // level 0's: none): sparse when small (right after a bottom-up level too: the
+  // compaction then zeroes the bottom-up input bitmap the sparse level writes
+  // into); p.cap: the global frontier edges a sparse chain stays live for.
+  const auto td_form = [&](double fmf) -> char {
+    if (xc_) {
+      if (list_max_ <= 0) return 'T';
+      if (counted_) {
+        // count-sized exchange: the largest lists cost nothing extra (cap 0:
+        // lists of a whole part, live for any level)
+        if (!exact && fmf > static_cast<double>(xsparse_lim_)) return 'T';
+        if (exact && !lists_unlimited_ && fmf > static_cast<double>(list_max_)) return 'T';
+        p.cap = lists_unlimited_ ? 0 : list_max_;
       // tiny levels: chains capped at fuse_cap (fused into one launch on a
       // direct transport; the same chains on every transport, so a shadow
       // replay follows its recording)
-      if (fuse_cap_ > 0 &&
-          (exact ? mf <= static_cast<double>(fuse_cap_) : mf <= static_cast<double>(opt_.xfuse_edges)))
-        *cap = fuse_cap_;
+        if (fuse_cap_ > 0 &&
+            (exact ? fmf <= static_cast<double>(fuse_cap_) : fmf <= static_cast<double>(opt_.xfuse_edges)))
+          p.cap = fuse_cap_;
+        return 'S';
+      }
+      // fixed-size exchange (cap + 1 ids per peer): lists sized for the
+      // level, list_cap_factor x the prediction (at least the actual edges
+      // of a re-enqueued level), a power of two >= 1024, and no larger than a
+      // bitmap slice's worth of ids (past that the dense form ships less)
+      const int64_t lim = std::min(list_max_, std::max<int64_t>(W_, 1024));
+      const double ids = std::max(1024.0, exact ? fmf : fmf * opt_.list_cap_factor);
+      if (ids > static_cast<double>(lim) || (!exact && fmf > static_cast<double>(xsparse_lim_))) return 'T';
+      int64_t c = 1024;
+      while (static_cast<double>(c) < ids) c <<= 1;
+      p.cap = std::min(c, lim);
       return 'S';
     }
-    // fixed-size exchange (cap + 1 ids per peer): lists sized for the
-    // level, list_cap_factor x the prediction (at least the actual edges
-    // of a re-enqueued level), a power of two >= 1024, and no larger than a
-    // bitmap slice's worth of ids (past that the dense form ships less)
-    const int64_t lim = std::min(list_max_, std::max<int64_t>(W_, 1024));
-    const double want = std::max(1024.0, exact ? mf : mf * opt_.list_cap_factor);
-    if (want > static_cast<double>(lim) || (!exact && mf > static_cast<double>(xsparse_lim_))) return 'T';
-    int64_t c = 1024;
-    while (static_cast<double>(c) < want) c <<= 1;
-    *cap = std::min(c, lim);
-    return 'S';
+    // right after a bottom-up level: sparse up to td_sparse_bu_edges, the
+    // chain live up to that many too (the prediction of a shrinking frontier
+    // overshoots, and that level reads the bottom-up output bitmap directly);
+    // elsewhere up to td_sparse_edges, live up to sparse_cap
+    const bool post_bu = p.pf == 'B' && opt_.td_sparse_bu_edges > opt_.td_sparse_edges;
+    int64_t lim = post_bu ? opt_.td_sparse_bu_edges : opt_.td_sparse_edges;
+    const int64_t live = post_bu && sparse_cap_ > 0 ? std::max(sparse_cap_, opt_.td_sparse_bu_edges) : sparse_cap_;
+    if (live > 0) lim = std::min(lim, live);  // (a sparse chain must stay live for fmf)
+    if (sparse_ && fmf <= static_cast<double>(lim)) {
+      p.cap = live;
+      return 'S';
+    }
+    // (binned only before the run's first bottom-up level)
+    const bool after_bu = first_bu_ >= 0 && first_bu_ < L;
+    // ... and not for a level the direct form does better: one of 16 x
+    // td_split_edges or more (split in parts), or one late enough for the
+    // unvisited filter (top-down only on RMAT-26: 0.5 B-edge level 5.6 -> 4.3
+    // ms, the filter levels 21.3 -> 10.8 and 0.72 -> 0.42 ms)
+    const bool huge = opt_.td_split_edges > 0 && fmf >= 16.0 * static_cast<double>(opt_.td_split_edges);
+    // (lateness is judged by the visited sum handed to the chain planned just
+    // before this one -- the chain a re-enqueue replaces, else the previous
+    // level's: the figures above were measured with that one)
+    const double seen = exact ? plans_[static_cast<size_t>(L)].vis_hint
+                              : L > 0 ? plans_[static_cast<size_t>(L - 1)].vis_hint : -1.0;
+    const bool late = opt_.td_unvis_edges > 0 && seen >= opt_.td_unvis_vis_frac * total;
+    return binned_ && !after_bu && !huge && !late && fmf >= static_cast<double>(opt_.td_bin_edges) ? 'X' : 'T';
+  };
+  p.form = want == 'B' ? 'B' : want == 'D' ? 'T' : td_form(std::max(mf, 0.0));
+  p.dir = p.form == 'B' ? 'B' : 'T';
+  // several ranks: the level's end in the chain's last kernel (a bottom-up
+  // chain: the hub kernels' fused finish)
+  p.end_ok = xc_ && cells_fit_ && (p.form != 'B' || gv_.nhubs > 0);
+  // (the pushed slices are copied in by hub_gather: graphs with hubs)
+  p.want_push = p.gather && opt_.direct_frontier && gv_.nhubs > 0 && (p.form == 'T' || p.form == 'B');
+
+  if (p.form == 'T' || p.form == 'X') p.listed = sparse_ && (p.pf == 'S' || p.pf == 'I');
+  if (p.form == 'T') {
+    // late large levels: the unvisited filter (launched next to the plain
+    // variant; the filter's density picks the one that runs)
+    // (and, with the count of vertices with an edge known, a filter expected
+    // at most 1.5 x td_unvis_max_density dense: u of the vertices unvisited,
+    // n / kUnvisBits per bit -- so a hub-heavy level whose visited edges are
+    // many but whose unvisited vertices are too launches nothing extra)
+    p.unvis = opt_.td_unvis_edges > 0 && mf >= static_cast<double>(opt_.td_unvis_edges) &&
+              vis >= opt_.td_unvis_vis_frac * total;
+    if (p.unvis && e_.n_active_ > 0 && reach >= 0) {
+      const double u = std::max(0.0, static_cast<double>(e_.n_active_) - reach) / static_cast<double>(gv_.n);
+      const double per_bit = std::max(1.0, static_cast<double>(gv_.n) / static_cast<double>(kUnvisBits));
+      p.unvis = 1.0 - std::pow(1.0 - std::min(u, 1.0), per_bit) <= 1.5 * opt_.td_unvis_max_density;
+    }
+    // large levels: the hubs' visited bits, staged in LDS by td_expand
+    // (skipped for levels predicted well below the filter's threshold: the
+    // snapshot kernel would only find its gate closed)
+    p.hub_filter = gv_.td_nhubs > 0 && opt_.td_hub_edges > 0 && e_.g_.td_hub_share() >= opt_.td_hub_min_share &&
+                   (mf < 0 || mf * 4.0 >= static_cast<double>(opt_.td_hub_edges));
+    // byte-map levels write the level itself (nothing to clear after)
+    // (a level past kNarrowMaxLevel would store the unreached byte: the usual
+    // path flags the overflow and the run is repeated wide)
+    p.direct = direct_ && L + 1 <= kNarrowMaxLevel;
+    // Hub marks become level bytes (hub_apply), which only the direct form's
+    // update reads back; the device picks the form by the level's edges.  So
+    // marks only when every level the hub filter can run on (>= td_hub_edges
+    // edges) is a direct one (>= byte_edges_); else unvisited hubs are decoded
+    // and claimed like any other target, in either form.  (Marked in a bitmap
+    // level, a hub got its level byte but never its visited and frontier
+    // bits: found again later, at a deeper level.)
+    p.hub_marks = p.direct && p.hub_filter && bytes_ok_ && byte_edges_ <= opt_.td_hub_edges;
+    // large level-byte levels (one rank): the level in parts, the claims so far
+    // ORed into visited between them (Options::td_split_edges)
+    // (not with the unvisited filter: a late level claims few vertices, and
+    // every part would stage the filter and launch both variants again --
+    // RMAT-22's level 4 87 -> 134 us in 4 parts)
+    if (p.direct && !p.unvis && !xc_ && opt_.td_split_edges > 0 && opt_.td_split_parts > 1 &&
+        mf >= static_cast<double>(opt_.td_split_edges))
+      p.parts = opt_.td_split_parts *
+                (mf >= 16.0 * static_cast<double>(opt_.td_split_edges) && gv_.n >= (int64_t(1) << 25) ? 2 : 1);
   }
-  const char pf = L == 0 ? 'I' : enq_form_[static_cast<size_t>(L - 1)];
-  // right after a bottom-up level: sparse up to td_sparse_bu_edges, the
-  // chain live up to that many too (the prediction of a shrinking frontier
-  // overshoots, and that level reads the bottom-up output bitmap directly);
-  // elsewhere up to td_sparse_edges, live up to sparse_cap
-  const bool post_bu = pf == 'B' && opt_.td_sparse_bu_edges > opt_.td_sparse_edges;
-  int64_t lim = post_bu ? opt_.td_sparse_bu_edges : opt_.td_sparse_edges;
-  const int64_t live = post_bu && sparse_cap_ > 0 ? std::max(sparse_cap_, opt_.td_sparse_bu_edges) : sparse_cap_;
-  if (live > 0) lim = std::min(lim, live);  // (a sparse chain must stay live for mf)
-  if (sparse_ && mf <= static_cast<double>(lim)) {
-    *cap = live;
-    return 'S';
+  if (p.form == 'S') {
+    // after a bottom-up level the output bitmap is that level's input: zeroed
+    // by the compaction (every other form leaves it clean)
+    p.compacted = p.pf == 'T' || p.pf == 'X' || p.pf == 'B';
+    // right after a bottom-up level: the kernel reads that level's output
+    // bitmap itself (no unit scan, no compaction); only the stale output bitmap
+    // is cleared first
+    p.from_bits = p.pf == 'B' && opt_.td_sparse_bits;
+    if (xc_) {
+      // the owners' side sized by its expected ids (a rank receives about
+      // mf (P - 1) / P^2 claims): ~512 per workgroup, up to td_apply_grid -- the
+      // large levels' latency-bound claims spread over every CU, a tiny level's
+      // launch stays small
+      const double est_mf = mf >= 0 ? mf : static_cast<double>(p.cap > 0 ? p.cap : list_max_);
+      const double est_ids = est_mf * static_cast<double>(P_ - 1) / (static_cast<double>(P_) * P_);
+      p.apply_grid =
+          std::max<int64_t>(1, std::min<int64_t>(opt_.td_apply_grid, static_cast<int64_t>(est_ids / 512.0) + 1));
+      // (ranks sharing a GPU with the waits inside the apply -- every workgroup
+      // spins on the peers' cells: at most 64 1024-thread workgroups over all of
+      // them, an eighth of the chip's residency, so a peer's td_sparse always
+      // finds CUs)
+      if (coresident_ > 1 && !split_waits_)
+        p.apply_grid = std::min<int64_t>(p.apply_grid, std::max(1, 64 / coresident_));
+      // a tiny level (its chain capped at fuse_cap): td_sparse's last workgroup
+      // also runs the owner side and the level end -- one launch (the direct
+      // level end is taken in the same order as unfused)
+      // (no frontier gather: that one is a bandwidth collective of its own)
+      p.fuse_ok = p.end_ok && !p.gather && fuse_cap_ > 0 && p.cap > 0 && p.cap <= fuse_cap_;
+    }
   }
-  bool after_bu = false;  // (binned only before the run's first bottom-up level)
-  for (int k = 0; k < L && !after_bu; ++k) after_bu = enq_form_[static_cast<size_t>(k)] == 'B';
-  // ... and not for a level the direct form does better: one of 16 x
-  // td_split_edges or more (split in parts), or one late enough for the
-  // unvisited filter (top-down only on RMAT-26: 0.5 B-edge level 5.6 -> 4.3
-  // ms, the filter levels 21.3 -> 10.8 and 0.72 -> 0.42 ms)
-  const bool huge = opt_.td_split_edges > 0 && mf >= 16.0 * static_cast<double>(opt_.td_split_edges);
-  const bool late = opt_.td_unvis_edges > 0 && vis_hint_ >= opt_.td_unvis_vis_frac * static_cast<double>(e_.total_directed_);
-  return binned_ && !after_bu && !huge && !late && mf >= static_cast<double>(opt_.td_bin_edges) ? 'X' : 'T';
+  if (p.form == 'B') {
+    p.whole_units = opt_.bu_whole_units;
+    // the third and later bottom-up levels of a run (few unvisited vertices
+    // left) scan whole units even on shards too small to fill the chip that
+    // way: shadow ranks of P = 4 on RMAT-26, those levels 28-31 -> 22-24 us,
+    // where the first two lost 4-10 % (profiles/r6_bu_whole_late_levels.txt)
+    if (p.whole_units == 0 && L >= 2 && p.pf == 'B' && plans_[static_cast<size_t>(L - 2)].form == 'B')
+      p.whole_units = 1;
+    p.follow_up = p.pf == 'B';
+    // a first bottom-up level: the hub cut (decided on the device from the
+    // frontier hubs' degrees hub_gather sums -- global, so the same on every
+    // rank), enqueued for levels predicted at <= bu_cut_mf_frac of the
+    // graph's edges (a first bottom-up level's non-hub frontier edges grow
+    // with its frontier: the larger ones never cut, and skip its launches).
+    // Several ranks (up to bu_cut_ranks): the remote claims as one bitmap
+    // all-to-all (xcut).
+    p.cut = gv_.nhubs > 0 && opt_.bu_cut_edges > 0 && p.pf != 'B' &&
+            (mf < 0 || mf <= opt_.bu_cut_mf_frac * total) && cut_shard_ok_;
+    p.xcut = p.cut && P_ > 1;
+  }
+  return p;
 }
 
 // the chain enqueued for level L is live for a level with direction `dir`
 // and mf global frontier edges
 bool DeviceLoop::chain_valid(int L, char dir, int64_t mf) const {
-  if (enq_dir_[L] != dir) return false;
-  return enq_form_[L] != 'S' || enq_cap_[L] <= 0 || mf <= enq_cap_[L];
+  const LevelPlan& p = plans_[static_cast<size_t>(L)];
+  if (p.dir != dir) return false;
+  return p.form != 'S' || p.cap <= 0 || mf <= p.cap;
 }
 
 // One prediction step: from a level with frontier (nf, mf), its
@@ -479,73 +674,54 @@ void DeviceLoop::predict(LevelCtrl& c, double nf, double mf, double pnf, double 
 
 // ---- emitters -------------------------------------------------------------------
 
-// mf_hint: the level's predicted (or, re-enqueued, actual) frontier edges
-// (< 0 unknown); gather (several ranks): the chain's collective also
-// all-gathers its output frontier, for a bottom-up level predicted next.
-void DeviceLoop::enqueue_level(int L, char d, int64_t cap, double mf_hint, bool gather) {
-  if (ht_) hmark("enqueue " + std::to_string(L) + d);
+// Emits the chain of plan p, which becomes its level's latest, and records it.
+void DeviceLoop::enqueue_level(const LevelPlan& p) {
+  const int L = p.level;
+  if (ht_) hmark("enqueue " + std::to_string(L) + p.form);
   comm_.set_level_tag(L);  // (a failed collective of this chain names its level)
-  if (static_cast<size_t>(L) >= enq_dir_.size()) {
+  if (static_cast<size_t>(L) >= plans_.size()) {
     e_.inject_fault(L);
-    enq_dir_.resize(static_cast<size_t>(L) + 1);
-    enq_form_.resize(static_cast<size_t>(L) + 1);
-    enq_cap_.resize(static_cast<size_t>(L) + 1);
-    enq_gather_.resize(static_cast<size_t>(L) + 1);
-    enq_fused_.resize(static_cast<size_t>(L) + 1);
-    enq_push_.resize(static_cast<size_t>(L) + 1);
-    evs_.resize(static_cast<size_t>(L) + 1, {-1, -1});
+    plans_.resize(static_cast<size_t>(L) + 1);
+    emitted_.resize(static_cast<size_t>(L) + 1);
   }
+  plans_[L] = p;
+  // (a re-enqueue may replace the first bottom-up chain by a top-down one:
+  // any later bottom-up chain is then its stale successor, replaced next)
+  if (p.form == 'B' && (first_bu_ < 0 || L < first_bu_)) first_bu_ = L;
+  if (p.form != 'B' && first_bu_ == L) first_bu_ = -1;
   Chain c;
-  c.L = L;
-  c.d = d;
-  // the previous level's form decides what hands this one its work list
-  c.pf = L == 0 ? 'I' : enq_form_[static_cast<size_t>(L - 1)];
-  // the input frontier is already global: all-gathered by the previous
-  // level's (or the seed's) collective
-  c.in_gathered = L == 0 ? seed_gather_ : enq_gather_[static_cast<size_t>(L - 1)] != 0;
-  enq_dir_[L] = d == 'B' ? 'B' : 'T';
-  enq_form_[L] = d;
-  enq_cap_[L] = d == 'S' ? cap : 0;
-  enq_gather_[L] = xc_ && gather;
-  // (the pushed slices are copied in by hub_gather: graphs with hubs; the
-  // table's parity is the level's -- see FrontierTable)
-  c.pull = L > 0 ? enq_push_[static_cast<size_t>(L - 1)] : nullptr;
-  c.push = enq_gather_[L] && opt_.direct_frontier && gv_.nhubs > 0 && (d == 'T' || d == 'B')
-               ? comm_.direct_frontier(static_cast<size_t>(W_), L & 1)
-               : nullptr;
-  enq_push_[L] = c.push;
-  res_.chains.push_back({L, d, enq_cap_[L], enq_gather_[L] != 0});
-  res_.chains.back().push = c.push != nullptr;
-  c.cap = enq_cap_[L];
-  c.guard = {e_.ctrl_.data(), enq_dir_[L], c.cap};
-  c.mf_hint = mf_hint;
-  c.cur = (L + 1) & 1;
+  c.p = p;
+  c.guard = {e_.ctrl_.data(), p.dir, p.cap};
+  // (the table's parity is the level's -- see FrontierTable)
+  c.pull = L > 0 ? emitted_[static_cast<size_t>(L - 1)].push : nullptr;
+  c.push = p.want_push ? comm_.direct_frontier(static_cast<size_t>(W_), L & 1) : nullptr;
   char trace_name[48];
-  std::snprintf(trace_name, sizeof(trace_name), "bfs.level %d %c (enqueue)", L, d);
+  std::snprintf(trace_name, sizeof(trace_name), "bfs.level %d %c (enqueue)", L, p.form);
   TraceRange trace_level(trace_name);
   const int ev0 = opt_.phase_timing ? be_.record_event() : -1;
   // several ranks, bottom-up: the input frontier to every rank -- normally
   // gathered already by the previous level's collective; a chain enqueued
   // after a top-down prediction gathers it here (not predicated: on a no-op
   // chain it only refreshes bits every owner already has)
-  if (xc_ && d == 'B') {
-    if (!c.in_gathered)
-      comm_.allgather(fr_own(c.cur), e_.frontier_[c.cur].data(), static_cast<size_t>(W_) * sizeof(word_t));
+  if (xc_ && p.form == 'B') {
+    if (!p.in_gathered)
+      comm_.allgather(fr_own(p.cur), e_.frontier_[p.cur].data(), static_cast<size_t>(W_) * sizeof(word_t));
     // (bu_merge_visited: the remote slices merged into the replicated
     // visited bitmap -- by hub_gather with hubs)
     if (opt_.bu_merge_visited && gv_.nhubs == 0)
-      be_.bitmap_or(e_.visited_.data(), e_.frontier_[c.cur].data(), GW_);
+      be_.bitmap_or(e_.visited_.data(), e_.frontier_[p.cur].data(), GW_);
   }
-  switch (d) {
+  switch (p.form) {
     case 'S': emit_sparse(c); break;
     case 'X': emit_binned(c); break;
     case 'T': emit_dense(c); break;
     default: emit_bottom_up(c); break;
   }
   if (!c.fused_scan) be_.scan_units(scan_args(L, c.guard));
-  enq_fused_[L] = c.fused_scan && d != 'S' && !c.folded;
-  if (xc_ && !c.level_ended) finish_ranks(L, c.guard, enq_gather_[L] && !c.push);
-  if (opt_.phase_timing) evs_[L] = {ev0, be_.record_event()};
+  if (xc_ && !c.level_ended) finish_ranks(L, c.guard, p.gather && !c.push);
+  emitted_[L] = {c.fused_scan && p.form != 'S' && !c.folded, c.push,
+                 {ev0, opt_.phase_timing ? be_.record_event() : -1}};
+  res_.chains.push_back({L, p.form, p.cap, p.gather, c.push != nullptr, p.unvis, p.parts, p.cut});
   if (ht_) hmark("enqueued " + std::to_string(L));
 }
 
@@ -553,8 +729,8 @@ void DeviceLoop::enqueue_level(int L, char d, int64_t cap, double mf_hint, bool 
 // vertex map, and the bitmap is zeroed as read (a later sparse level writes
 // into it).
 void DeviceLoop::compact(const Chain& c, word_t* clear_all) {
-  const int L = c.L;
-  if (L > 0 && enq_fused_[static_cast<size_t>(L - 1)]) {
+  const int L = c.p.level;
+  if (L > 0 && emitted_[static_cast<size_t>(L - 1)].scan_owed) {
     // the previous level only finished its totals: its unit prefixes now (no
     // finish; under this chain's guard: a no-op unless this chain is live)
     ScanArgs sa = scan_args(L - 1, c.guard);
@@ -563,14 +739,14 @@ void DeviceLoop::compact(const Chain& c, word_t* clear_all) {
   }
   CompactArgs ca;
   ca.g = gv_;
-  ca.frontier = fr_own(c.cur);
+  ca.frontier = fr_own(c.p.cur);
   ca.words = W_;
   ca.unit_cnt_off = e_.unit_cnt_.data();
   ca.unit_deg_off = e_.unit_deg_.data();
   ca.part_cnt = e_.part_cnt_.data();
   ca.part_deg = e_.part_deg_.data();
   ca.wl = work_list(L);
-  if (sparse_) ca.clear = fr_own(c.cur);
+  if (sparse_) ca.clear = fr_own(c.p.cur);
   ca.clear_all = clear_all;
   ca.guard = c.guard;
   be_.compact_frontier(ca);
@@ -582,23 +758,17 @@ void DeviceLoop::compact(const Chain& c, word_t* clear_all) {
 // exchanged count-sized (or stored by the kernel into the owners' windows),
 // and td_sparse_apply settles the received ids.
 void DeviceLoop::emit_sparse(Chain& c) {
-  const int L = c.L;
+  const LevelPlan& p = c.p;
+  const int L = p.level;
   DBFS_CHECK(sparse_, "sparse top-down level without sparse support");
-  // after a bottom-up level the output bitmap is that level's input: zeroed
-  // by the compaction (every other form leaves it clean)
-  const bool compacted = c.pf == 'T' || c.pf == 'X' || c.pf == 'B';
-  // right after a bottom-up level: the kernel reads that level's output
-  // bitmap itself (no unit scan, no compaction); only the stale output bitmap
-  // is cleared first
-  const bool from_bits = c.pf == 'B' && opt_.td_sparse_bits;
-  if (from_bits) be_.memset_async(fr_own(c.cur ^ 1), 0, static_cast<size_t>(W_) * sizeof(word_t));
-  else if (compacted) compact(c, c.pf == 'B' ? fr_own(c.cur ^ 1) : nullptr);
+  if (p.from_bits) be_.memset_async(fr_own(p.cur ^ 1), 0, static_cast<size_t>(W_) * sizeof(word_t));
+  else if (p.compacted) compact(c, p.pf == 'B' ? fr_own(p.cur ^ 1) : nullptr);
   TdSparseArgs sp;
   sp.g = gv_;
   sp.in = work_list(L);
   sp.dev_stats = sblk(L - 1);
-  sp.frontier_in = fr_own(c.cur);
-  sp.frontier_out = fr_own(c.cur ^ 1);
+  sp.frontier_in = fr_own(p.cur);
+  sp.frontier_out = fr_own(p.cur ^ 1);
   sp.visited = e_.visited_.data();
   sp.out = e_.level_out(L + 1);
   sp.next = work_list(L + 1);
@@ -609,8 +779,8 @@ void DeviceLoop::emit_sparse(Chain& c) {
   sp.stamp = stamp(L);
   sp.grid = std::max<int64_t>(1, opt_.td_sparse_grid);
   sp.late_ticks = late_ticks_;
-  sp.first = !compacted || from_bits;
-  if (from_bits) {
+  sp.first = !p.compacted || p.from_bits;
+  if (p.from_bits) {
     sp.from_bits = true;
     sp.words = W_;
     sp.group_ticket = group_tickets();
@@ -623,38 +793,20 @@ void DeviceLoop::emit_sparse(Chain& c) {
   // remote claims to their owners' lists, the lists (count-sized) to their
   // owners, the received ids settled there; the totals go to the collective
   // (no decision in the kernels)
-  DBFS_CHECK(list_max_ > 0 && c.cap <= list_max_, "sparse chain without owner lists");
+  DBFS_CHECK(list_max_ > 0 && p.cap <= list_max_, "sparse chain without owner lists");
   sp.lists = e_.dl_send_lists_.data();
   sp.list_stride = e_.list_stride_;
   sp.part = part_.part;
   sp.stamp.mailbox = nullptr;
   // the exchange itself: by the two kernels through the peers' windows
   // (direct), or a collective between them
-  const size_t lcap = static_cast<size_t>(c.cap > 0 ? c.cap : list_max_);
+  const size_t lcap = static_cast<size_t>(p.cap > 0 ? p.cap : list_max_);
   const bool direct = comm_.direct_lists(lcap, &sp.direct);
   sp.nranks = P_;
-  // the owners' side sized by its expected ids (a rank receives about
-  // mf (P - 1) / P^2 claims): ~512 per workgroup, up to td_apply_grid -- the
-  // large levels' latency-bound claims spread over every CU, a tiny level's
-  // launch stays small
-  const double est_mf = c.mf_hint >= 0 ? c.mf_hint : static_cast<double>(c.cap > 0 ? c.cap : list_max_);
-  const double est_ids = est_mf * static_cast<double>(P_ - 1) / (static_cast<double>(P_) * P_);
-  int64_t apply_grid =
-      std::max<int64_t>(1, std::min<int64_t>(opt_.td_apply_grid, static_cast<int64_t>(est_ids / 512.0) + 1));
-  // (ranks sharing a GPU with the waits inside the apply -- every workgroup
-  // spins on the peers' cells: at most 64 1024-thread workgroups over all of
-  // them, an eighth of the chip's residency, so a peer's td_sparse always
-  // finds CUs)
-  if (comm_.coresident() > 1 && !comm_.split_waits())
-    apply_grid = std::min<int64_t>(apply_grid, std::max(1, 64 / comm_.coresident()));
   // the level's end folded into the apply's last workgroup (no frontier
   // gather: that one is a bandwidth collective of its own)
-  // (the cells carry < 2^32 new vertices and < 2^40 degrees per rank)
-  const bool end_ok = direct && cells_fit() && !enq_gather_[L];
-  // a tiny level (its chain capped at fuse_cap): td_sparse's last workgroup
-  // also runs the owner side and the level end -- one launch (the direct
-  // level end is taken in the same order as unfused)
-  sp.fuse_apply = end_ok && fuse_cap_ > 0 && c.cap > 0 && c.cap <= fuse_cap_;
+  const bool end_ok = direct && p.end_ok && !p.gather;
+  sp.fuse_apply = direct && p.fuse_ok;
   if (sp.fuse_apply) {
     sp.recv_lists = nullptr;
     if (comm_.direct_level_end(2, &sp.end)) {
@@ -664,7 +816,7 @@ void DeviceLoop::emit_sparse(Chain& c) {
       sp.fuse_apply = false;  // (not taken: the level ends in its collective)
     }
     be_.td_sparse(sp);
-    sp.grid = apply_grid;
+    sp.grid = p.apply_grid;
     if (!c.level_ended) be_.td_sparse_apply(sp);
     return;
   }
@@ -677,11 +829,11 @@ void DeviceLoop::emit_sparse(Chain& c) {
     sp.fin = finish_args(L, c.guard);
     c.level_ended = true;
   }
-  sp.grid = apply_grid;
+  sp.grid = p.apply_grid;
   // ranks sharing a GPU: the wait for the peers' cells as a one-wave launch
   // first, so the apply's grid never spins in every workgroup while a peer's
   // td_sparse still needs CUs (Comm::split_waits)
-  if (direct && comm_.split_waits()) be_.direct_prewait(sp.direct);
+  if (direct && split_waits_) be_.direct_prewait(sp.direct);
   be_.td_sparse_apply(sp);
 }
 
@@ -689,14 +841,14 @@ void DeviceLoop::emit_sparse(Chain& c) {
 // per bin in LDS; a sparse level (or the seed) handed over the work list,
 // else compact.
 void DeviceLoop::emit_binned(Chain& c) {
-  const int L = c.L;
-  const bool listed = sparse_ && (c.pf == 'S' || c.pf == 'I');
-  if (!listed) compact(c, nullptr);
+  const LevelPlan& p = c.p;
+  const int L = p.level;
+  if (!p.listed) compact(c, nullptr);
   BinArgs xa;
   xa.g = gv_;
   xa.in = work_list(L);
   xa.dev_stats = sblk(L - 1);
-  if (listed) xa.clear_frontier = fr_own(c.cur);
+  if (p.listed) xa.clear_frontier = fr_own(p.cur);
   xa.guard = c.guard;
   xa.shift = bin_shift_;
   xa.nbins = static_cast<int>(nbins_);
@@ -705,17 +857,17 @@ void DeviceLoop::emit_binned(Chain& c) {
   xa.cnt = e_.bin_cnt_.data();
   xa.buf = e_.bin_buf_.data();
   xa.visited = e_.visited_.data() + me_ * W_;
-  xa.frontier = fr_own(c.cur ^ 1);
+  xa.frontier = fr_own(p.cur ^ 1);
   xa.words = W_;
   be_.td_binned(xa);
   // levels and unit statistics of the new frontier (already claimed)
   UpdateArgs tu = ua_;
-  tu.cand = fr_own(c.cur ^ 1);
+  tu.cand = fr_own(p.cur ^ 1);
   tu.cand_bytes = nullptr;
   tu.nchunks = 1;
   tu.clear_cand = false;
   tu.force = true;
-  tu.frontier = fr_own(c.cur ^ 1);
+  tu.frontier = fr_own(p.cur ^ 1);
   tu.out.new_level = L + 1;
   tu.guard = c.guard;
   be_.update_frontier(tu);
@@ -728,14 +880,13 @@ void DeviceLoop::emit_binned(Chain& c) {
 // (A first version with one workgroup per 4 units and totals atomics on one
 // address: level 1 of RMAT-26 38 -> 117 us.)
 void DeviceLoop::fuse_update(Chain& c, UpdateArgs& tu) {
-  if (!e_.td_tot_.data()) e_.td_tot_ = DBuf<int64_t>(be_, static_cast<size_t>(2 * kMaxFusedGrid + 2 * kFusedGroups));
   tu.fuse_scan = true;
-  tu.scan = scan_args(c.L, c.guard);
+  tu.scan = scan_args(c.p.level, c.guard);
   // graphs of at most kFoldScanUnits units: the next compaction's unit
   // prefixes too (one scan_units launch less per dense level)
   tu.fold_scan = e_.nunits_ <= kFoldScanUnits;
   c.folded = tu.fold_scan;
-  tu.tot = e_.td_tot_.data();
+  tu.tot = scratch(e_.td_tot_, static_cast<size_t>(2 * kMaxFusedGrid + 2 * kFusedGroups), false);
   tu.group_ticket = group_tickets();
   c.fused_scan = true;
 }
@@ -745,13 +896,13 @@ void DeviceLoop::fuse_update(Chain& c, UpdateArgs& tu) {
 // large levels test hub targets in an LDS snapshot) -> [several ranks: the
 // candidate slices to their owners] -> update (fused finish).
 void DeviceLoop::emit_dense(Chain& c) {
-  const int L = c.L;
-  const bool listed = sparse_ && (c.pf == 'S' || c.pf == 'I');
-  if (!listed) compact(c, nullptr);
+  const LevelPlan& p = c.p;
+  const int L = p.level;
+  if (!p.listed) compact(c, nullptr);
   TdArgs ta;
   ta.g = gv_;
   ta.in = work_list(L);
-  if (listed) ta.clear_frontier = fr_own(c.cur);
+  if (p.listed) ta.clear_frontier = fr_own(p.cur);
   ta.visited = e_.visited_.data();
   ta.guard = c.guard;
   ta.dev_stats = sblk(L - 1);
@@ -760,105 +911,52 @@ void DeviceLoop::emit_dense(Chain& c) {
   UpdateArgs tu = ua_;
   ta.next = e_.next_.data();
   ta.next_bytes = e_.next_bytes_.data();
-  // late large levels: the unvisited filter (launched next to the plain
-  // variant; the filter's density picks the one that runs)
-  // (and, with the count of vertices with an edge known, a filter expected
-  // at most 1.5 x td_unvis_max_density dense: u of the vertices unvisited,
-  // n / kUnvisBits per bit -- so a hub-heavy level whose visited edges are
-  // many but whose unvisited vertices are too launches nothing extra)
-  bool unvis = opt_.td_unvis_edges > 0 && c.mf_hint >= static_cast<double>(opt_.td_unvis_edges) &&
-               vis_hint_ >= opt_.td_unvis_vis_frac * static_cast<double>(e_.total_directed_);
-  if (unvis && e_.n_active_ > 0 && reach_hint_ >= 0) {
-    const double u = std::max(0.0, static_cast<double>(e_.n_active_) - reach_hint_) / static_cast<double>(gv_.n);
-    const double per_bit = std::max(1.0, static_cast<double>(gv_.n) / static_cast<double>(kUnvisBits));
-    unvis = 1.0 - std::pow(1.0 - std::min(u, 1.0), per_bit) <= 1.5 * opt_.td_unvis_max_density;
-  }
-  if (unvis) {
-    res_.chains.back().unvis = true;
-    if (!e_.unvis_.data()) {
-      e_.unvis_ = DBuf<word_t>(be_, static_cast<size_t>(kUnvisWords));
-      e_.unvis_pop_ = DBuf<uint32_t>(be_, static_cast<size_t>(kUnvisChunks));
-    }
+  if (p.unvis) {
     UnvisArgs uv;
     uv.visited = e_.visited_.data();
     uv.n = gv_.n;
     uv.mult = unvis_mult(gv_.n);
-    uv.out = e_.unvis_.data();
-    uv.pop = e_.unvis_pop_.data();
+    uv.out = scratch(e_.unvis_, static_cast<size_t>(kUnvisWords), false);
+    uv.pop = scratch(e_.unvis_pop_, static_cast<size_t>(kUnvisChunks), false);
     uv.guard = c.guard;
     be_.unvis_filter(uv);
-    ta.unvis = e_.unvis_.data();
+    ta.unvis = uv.out;
     ta.unvis_mult = uv.mult;
     ta.unvis_pop = uv.pop;
     ta.unvis_max_density = opt_.td_unvis_max_density;
   }
-  // (skipped for levels predicted well below the filter's threshold: the
-  // snapshot kernel would only find its gate closed)
-  if (gv_.td_nhubs > 0 && opt_.td_hub_edges > 0 && e_.g_.td_hub_share() >= opt_.td_hub_min_share &&
-      (c.mf_hint < 0 || c.mf_hint * 4.0 >= static_cast<double>(opt_.td_hub_edges))) {
-    // large levels: the hubs' visited bits, staged in LDS by td_expand
-    if (!e_.td_hub_vis_.data())
-      e_.td_hub_vis_ = DBuf<word_t>(be_, static_cast<size_t>(div_up(gv_.td_nhubs, kWordBits)));
+  if (p.hub_filter) {
     HubVisitedArgs hv;
     hv.g = gv_;
     hv.visited = e_.visited_.data();
-    hv.out = e_.td_hub_vis_.data();
+    hv.out = scratch(e_.td_hub_vis_, static_cast<size_t>(div_up(gv_.td_nhubs, kWordBits)), false);
     hv.guard = c.guard;
     hv.min_edges = opt_.td_hub_edges;
     hv.vis_frac = opt_.td_hub_vis_frac;
     be_.hub_visited(hv);
-    ta.td_hub_vis = e_.td_hub_vis_.data();
+    ta.td_hub_vis = hv.out;
     ta.td_hub_min_edges = opt_.td_hub_edges;
     ta.td_hub_vis_frac = opt_.td_hub_vis_frac;
   }
-  // (a level past kNarrowMaxLevel would store the unreached byte: the usual
-  // path flags the overflow and the run is repeated wide)
   ta.out = e_.level_out(L + 1);
-  if (direct_ && L + 1 <= kNarrowMaxLevel) {
-    // byte-map levels write the level itself (nothing to clear after)
+  if (p.direct) {
     ta.level_direct = ta.out.level8;
     tu.level_direct = ta.out.level8;
-    // Hub marks become level bytes (hub_apply), which only the direct form's
-    // update reads back; the device picks the form by the level's edges.  So
-    // marks only when every level the hub filter can run on (>= td_hub_edges
-    // edges) is a direct one (>= byte_edges_); else unvisited hubs are decoded
-    // and claimed like any other target, in either form.  (Marked in a bitmap
-    // level, a hub got its level byte but never its visited and frontier
-    // bits: found again later, at a deeper level.)
-    if (ta.td_hub_vis && bytes_ok_ && byte_edges_ <= opt_.td_hub_edges) {
-      if (!e_.td_hub_mark_.data()) {
-        e_.td_hub_mark_ = DBuf<uint8_t>(be_, static_cast<size_t>(kTdMaxHubs));
-        be_.memset_async(e_.td_hub_mark_.data(), 0, e_.td_hub_mark_.bytes());
-      }
-      ta.td_hub_mark = e_.td_hub_mark_.data();
-    }
+    if (p.hub_marks) ta.td_hub_mark = scratch(e_.td_hub_mark_, static_cast<size_t>(kTdMaxHubs), true);
   }
-  // large level-byte levels (one rank): the level in parts, the claims so far
-  // ORed into visited between them (Options::td_split_edges)
-  // (not with the unvisited filter: a late level claims few vertices, and
-  // every part would stage the filter and launch both variants again --
-  // RMAT-22's level 4 87 -> 134 us in 4 parts)
-  const int parts = (ta.level_direct && !unvis && !xc_ && opt_.td_split_edges > 0 && opt_.td_split_parts > 1 &&
-                     c.mf_hint >= static_cast<double>(opt_.td_split_edges))
-                        ? opt_.td_split_parts * (c.mf_hint >= 16.0 * static_cast<double>(opt_.td_split_edges) &&
-                                                         gv_.n >= (int64_t(1) << 25)
-                                                     ? 2
-                                                     : 1)
-                        : 1;
-  if (parts > 1) {
-    res_.chains.back().split = parts;
+  if (p.parts > 1) {
     RefreshArgs ra;
     ra.out = ta.out;
     ra.visited = e_.visited_.data();
     ra.words = GW_;
     ra.guard = c.guard;
-    ta.split_k = parts;
-    for (int i = 0; i < parts; ++i) {
+    ta.split_k = p.parts;
+    for (int i = 0; i < p.parts; ++i) {
       ta.split_i = i;
       be_.td_expand(ta);
       // (the input list's frontier words cleared, the level stamped: once)
       ta.clear_frontier = nullptr;
-      if (i + 1 < parts) be_.refresh_visited(ra);
+      if (i + 1 < p.parts) be_.refresh_visited(ra);
     }
   } else {
     be_.td_expand(ta);
@@ -894,8 +992,8 @@ void DeviceLoop::emit_dense(Chain& c) {
   }
   // (a split level: visited already holds the earlier parts' claims -- every
   // level byte of this level is a new vertex, as every `next` bit is)
-  tu.force = parts > 1;
-  tu.frontier = fr_own(c.cur ^ 1);
+  tu.force = p.parts > 1;
+  tu.frontier = fr_own(p.cur ^ 1);
   tu.out.new_level = L + 1;
   tu.guard = c.guard;
   tu.push = c.push;
@@ -906,7 +1004,7 @@ void DeviceLoop::emit_dense(Chain& c) {
   fuse_update(c, tu);
   // several ranks: the level's end in the same last workgroup (no frontier
   // gathered, or a pushed one)
-  if (xc_ && cells_fit() && (!enq_gather_[L] || c.push) && comm_.direct_level_end(2, &tu.end)) {
+  if (p.end_ok && (!p.gather || c.push) && comm_.direct_level_end(2, &tu.end)) {
     tu.fin = finish_args(L, c.guard);
     c.level_ended = true;
   }
@@ -919,43 +1017,36 @@ void DeviceLoop::emit_dense(Chain& c) {
 // frontier top-down)] -> bu_step (fused finish; several ranks: the level end
 // in its last workgroup when nothing is gathered).
 void DeviceLoop::emit_bottom_up(Chain& c) {
-  const int L = c.L;
+  const LevelPlan& p = c.p;
+  const int L = p.level;
   BuArgs ba;
   ba.g = gv_;
   ba.visited = e_.visited_.data() + me_ * W_;
-  ba.frontier = e_.frontier_[c.cur].data();
-  ba.new_frontier = fr_own(c.cur ^ 1);
+  ba.frontier = e_.frontier_[p.cur].data();
+  ba.new_frontier = fr_own(p.cur ^ 1);
   ba.out = e_.level_out(L + 1);
   ba.words = W_;
   ba.lane_limit = opt_.bu_lane_limit;
-  ba.whole_units = opt_.bu_whole_units;
-  // the third and later bottom-up levels of a run (few unvisited vertices
-  // left) scan whole units even on shards too small to fill the chip that
-  // way: shadow ranks of P = 4 on RMAT-26, those levels 28-31 -> 22-24 us,
-  // where the first two lost 4-10 % (profiles/r6_bu_whole_late_levels.txt)
-  if (ba.whole_units == 0 && L >= 2 && enq_form_[static_cast<size_t>(L - 1)] == 'B' &&
-      enq_form_[static_cast<size_t>(L - 2)] == 'B')
-    ba.whole_units = 1;
+  ba.whole_units = p.whole_units;
   ba.small_waves = opt_.bu_small_waves;
   ba.zdeg = e_.zdeg_.data() + me_ * W_;
-  ba.follow_up = c.pf == 'B';
+  ba.follow_up = p.follow_up;
   ba.unit_cnt = e_.unit_cnt_.data();
   ba.unit_deg = e_.unit_deg_.data();
   ba.guard = c.guard;
   ba.push = c.push;
   ba.push_rank = me_;
   ba.push_nranks = P_;
-  bool cut = false;  // a hub-cut level was enqueued
   if (gv_.nhubs > 0) {
     HubGatherArgs hg;
     hg.g = gv_;
-    hg.frontier = e_.frontier_[c.cur].data();
+    hg.frontier = e_.frontier_[p.cur].data();
     hg.hub_front = e_.hub_front_.data();
     hg.guard = c.guard;
     if (c.pull) {
       // the peers' slices pushed by the previous level's kernels
       hg.pull = c.pull;
-      hg.pull_out = e_.frontier_[c.cur].data();
+      hg.pull_out = e_.frontier_[p.cur].data();
       hg.pull_rank = me_;
       hg.pull_nranks = P_;
       hg.pull_words = W_;
@@ -966,60 +1057,28 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
       hg.visited = e_.visited_.data();
       hg.words = GW_;
     }
-    // a first bottom-up level: the hub cut (decided on the device from the
-    // frontier hubs' degrees hub_gather sums -- global, so the same on every
-    // rank), enqueued for levels predicted at <= bu_cut_mf_frac of the
-    // graph's edges (a first bottom-up level's non-hub frontier edges grow
-    // with its frontier: the larger ones never cut, and skip its launches).
-    // Several ranks (up to bu_cut_ranks): the remote claims as one bitmap
-    // all-to-all (xcut).
-    const bool xcut = P_ > 1;
-    // (several ranks: every condition the same on every rank -- the chain
-    // then carries the claims' collective)
-    const bool shard_ok = P_ == 1 ? gv_.hub_bits && gv_.nz_rec && gv_.unit_base && gv_.nz_pref && gv_.nz_row_off &&
-                                        gv_.head && ba.zdeg
-                                  : xc_ && P_ <= opt_.bu_cut_ranks && e_.g_.rec_all();
-    cut = opt_.bu_cut_edges > 0 && c.pf != 'B' &&
-          (c.mf_hint < 0 || c.mf_hint <= opt_.bu_cut_mf_frac * static_cast<double>(e_.total_directed_)) && shard_ok;
-    if (cut) {
-      if (!e_.cut_part_.data()) {
-        e_.cut_part_ = DBuf<int64_t>(be_, static_cast<size_t>(std::max<int64_t>(div_up(gv_.nhubs, int64_t(64)), kHgCopyGrid)));
-        e_.cut_flag_ = DBuf<int>(be_, 1);
-        e_.cut_ticket_ = DBuf<unsigned>(be_, 1);
-        be_.memset_async(e_.cut_ticket_.data(), 0, e_.cut_ticket_.bytes());
-      }
-      hg.cut_part = e_.cut_part_.data();
+    if (p.cut) {
+      hg.cut_part = scratch(e_.cut_part_,
+                            static_cast<size_t>(std::max<int64_t>(div_up(gv_.nhubs, int64_t(64)), kHgCopyGrid)), false);
       hg.cut_edges = opt_.bu_cut_edges;
-      hg.cut_flag = e_.cut_flag_.data();
-      hg.cut_ticket = e_.cut_ticket_.data();
+      hg.cut_flag = scratch(e_.cut_flag_, 1, false);
+      hg.cut_ticket = scratch(e_.cut_ticket_, 1, true);
     }
     be_.hub_gather(hg);
     ba.hub_front = e_.hub_front_.data();
-    if (cut) {
+    if (p.cut) {
       ba.cut_edges = opt_.bu_cut_edges;
       ba.cut_flag = e_.cut_flag_.data();
-      if (!ba.out.level8) {
-        // wide levels: claims in a byte array of their own (kept zero)
-        if (!e_.cut_claim_.data()) {
-          e_.cut_claim_ = DBuf<uint8_t>(be_, static_cast<size_t>(W_ * kWordBits));
-          be_.memset_async(e_.cut_claim_.data(), 0, e_.cut_claim_.bytes());
-        }
-        ba.cut_claim = e_.cut_claim_.data();
-      }
-      res_.chains.back().cut = true;
-      if (xcut) {
-        // the remote claims: bytes of the global byte map (zero between its
-        // users: every pack clears what it read)
-        if (!e_.next_bytes_.data()) {
-          e_.next_bytes_ = DBuf<uint8_t>(be_, static_cast<size_t>(GW_) * kWordBits);
-          be_.memset_async(e_.next_bytes_.data(), 0, e_.next_bytes_.bytes());
-        }
-        ba.cut_bytes = e_.next_bytes_.data();
+      // wide levels: claims in a byte array of their own (kept zero)
+      if (!ba.out.level8) ba.cut_claim = scratch(e_.cut_claim_, static_cast<size_t>(W_ * kWordBits), true);
+      if (p.xcut) {
+        // the remote claims: bytes of the global byte map
+        ba.cut_bytes = byte_map();
         ba.cut_vis = e_.visited_.data();
         ba.cut_word_off = me_ * W_;
       }
       be_.bu_cut_prep(ba);
-      if (xcut) {
+      if (p.xcut) {
         // ... packed per owner into `next`, one bitmap all-to-all (a
         // collective: on a plain or no-op chain too, then empty), merged on
         // the owners; `next` re-zeroed by the merge
@@ -1044,16 +1103,15 @@ void DeviceLoop::emit_bottom_up(Chain& c) {
   // the level's totals (and with one rank its finish: direction decision,
   // mailbox stamp) in the bottom-up kernel's last-arriving workgroup instead
   // of a scan launch; the unit prefixes only if a top-down chain follows
-  if (!e_.bu_tot_.data()) e_.bu_tot_ = DBuf<int64_t>(be_, static_cast<size_t>(2 * kMaxFusedGrid));
   ba.fuse_scan = true;
   ba.scan = scan_args(L, c.guard);
-  ba.tot = e_.bu_tot_.data();
+  ba.tot = scratch(e_.bu_tot_, static_cast<size_t>(2 * kMaxFusedGrid), false);
   c.fused_scan = true;
   // several ranks: the level's end in the kernel's last workgroup too (no
   // frontier gather; the hub kernels' fused finish) -- on a hub-cut level
   // in whichever of its two kernels the decision runs (the plain one on a
   // no-op chain)
-  if (xc_ && cells_fit() && gv_.nhubs > 0 && (!enq_gather_[L] || c.push) && comm_.direct_level_end(2, &ba.end)) {
+  if (p.end_ok && (!p.gather || c.push) && comm_.direct_level_end(2, &ba.end)) {
     ba.fin = finish_args(L, c.guard);
     c.level_ended = true;
   }
@@ -1156,16 +1214,14 @@ RunResult DeviceLoop::run() {
   LevelCtrl hc = init_;  // host mirror for the prediction
   int64_t prev_nf = 0, prev_mf = 0;
   bool any_bu = init_.dir == 'B';  // a bottom-up level was decided (the rising phase is over)
-  {
-    int64_t cap0 = 0;
-    const char f0 = init_.dir == 'B' ? 'B' : td_form(0, 0.0, &cap0, false);
-    enqueue_level(0, f0, cap0, -1.0, init_.dir == 'B');
-  }
+  // the non-predicting loop's chain: dense top-down or bottom-up, nothing known
+  const auto plain = [&](int lv, char dir) {
+    return plan_level(lv, dir == 'B' ? 'B' : 'D', -1.0, false, dir == 'B', -1.0, -1.0);
+  };
+  enqueue_level(plan_level(0, static_cast<char>(init_.dir), -1.0, false, init_.dir == 'B', -1.0, -1.0));
   for (int L = 0;; ++L) {
-    if (!opt_.device_loop_predict) {
-      // dense top-down or bottom-up, one more level ahead
-      enqueue_level(L + 1, enq_dir_[L], 0, -1.0, enq_dir_[L] == 'B');
-    }
+    // (one more level ahead, in level L's direction)
+    if (!opt_.device_loop_predict) enqueue_level(plain(L + 1, plans_[L].dir));
     const volatile LevelMailbox* mb = nullptr;
     try {
       mb = wait_stamp(L - 1);
@@ -1183,8 +1239,8 @@ RunResult DeviceLoop::run() {
     if (!valid) ++res_.mispredicts;
     if (!opt_.device_loop_predict) {
       if (!valid) {
-        enqueue_level(L, actual, 0, -1.0, actual == 'B');
-        enqueue_level(L + 1, actual, 0, -1.0, actual == 'B');
+        enqueue_level(plain(L, actual));
+        enqueue_level(plain(L + 1, actual));
       }
       continue;
     }
@@ -1203,20 +1259,13 @@ RunResult DeviceLoop::run() {
     predict(hc2, enf, emf, static_cast<double>(nf), static_cast<double>(mf), static_cast<double>(mb->reached) + enf,
             false, !any_bu && d1 != 'B', &enf2, &emf2);
     const char d2 = static_cast<char>(hc2.dir);
-    if (!valid) {
-      int64_t cap = 0;
-      const char f = actual == 'B' ? 'B' : td_form(L, static_cast<double>(mf), &cap, true);
-      vis_hint_ = static_cast<double>(mb->vis_deg);  // (exact: level L's start)
-      reach_hint_ = static_cast<double>(mb->reached);
-      enqueue_level(L, f, cap, static_cast<double>(mf), d1 == 'B');
-    }
+    const double vis = static_cast<double>(mb->vis_deg), reached = static_cast<double>(mb->reached);
+    // (exact: level L's start)
+    if (!valid) enqueue_level(plan_level(L, actual, static_cast<double>(mf), true, d1 == 'B', vis, reached));
     prev_nf = nf;
     prev_mf = mf;
-    int64_t lcap = 0;
-    const char f = d1 == 'B' ? 'B' : td_form(L + 1, emf, &lcap, false);
-    vis_hint_ = static_cast<double>(mb->vis_deg) + emf;  // (level L + 1's frontier joins visited)
-    reach_hint_ = static_cast<double>(mb->reached) + enf;
-    enqueue_level(L + 1, f, lcap, emf, d2 == 'B');
+    // (level L + 1's frontier joins visited)
+    enqueue_level(plan_level(L + 1, d1, emf, false, d2 == 'B', vis + emf, reached + enf));
   }
   // The traversal is complete once the last stamp is seen: the stamping
   // workgroup ran after all of that level's work (and every earlier level's).
@@ -1261,7 +1310,8 @@ RunResult DeviceLoop::collect(int nlev, std::chrono::steady_clock::time_point t1
     r.frontier = recs[L].n_f;
     r.frontier_edges = recs[L].m_f;
     r.discovered = recs[L].discovered;
-    if (opt_.phase_timing && static_cast<size_t>(L) < evs_.size()) r.ms = be_.elapsed_ms(evs_[L].first, evs_[L].second);
+    if (opt_.phase_timing && static_cast<size_t>(L) < emitted_.size())
+      r.ms = be_.elapsed_ms(emitted_[L].ev.first, emitted_[L].ev.second);
     // device-clock times (kernels stamp them; no events, no overhead)
     if (khz > 0 && recs[L].t0 != 0 && recs[L].t1 >= recs[L].t0) {
       if (!opt_.phase_timing) r.ms = static_cast<double>(recs[L].t1 - recs[L].t0) / khz;

@@ -7,6 +7,7 @@ change levels, records or totals.  Each run is compared with the host loop,
 which has no chains, and with the sequential oracle."""
 import numpy as np
 
+import chain_plans
 import distributed_cuda_bfs_amd as dbfs
 
 MODE = "do"
@@ -66,6 +67,7 @@ def check_option_set(rt, name):
         dev.engine.set_option(k, v)
     assert dict(dev.engine.get_options())["device_loop"] == 1.0
     forms = set()
+    runs = []
     for src in roots:
         oracle, host_levels, b = ref[src]
         a = dev.run(src)
@@ -74,6 +76,8 @@ def check_option_set(rt, name):
         assert _strip(a) == _strip(b), (name, src)
         assert (a.reached, a.edges, a.depth) == (b.reached, b.edges, b.depth), (name, src)
         forms |= noop_forms(a)
+        runs.append(a)
+    chain_plans.check("gpu" if rt.is_gpu else "cpu", chain_plans.key("chain_guard", name), runs)
     print(f"chain guard: option set {name}: no-op chain forms {sorted(forms)}")
     _results[(id(rt), name)] = forms
     return forms

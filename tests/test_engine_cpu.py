@@ -7,6 +7,7 @@ device-side Graph500 validation.
 import numpy as np
 import pytest
 
+import chain_plans
 import distributed_cuda_bfs_amd as dbfs
 from distributed_cuda_bfs_amd.parallel.runtime import init_runtime, run_virtual_ranks
 
@@ -286,6 +287,7 @@ def test_device_loop_matches_host_loop(rt, mode, predict):
     host = dbfs.BFS(p, rt, mode=mode)
     host.engine.set_option("device_loop", 0)
     assert dict(dev.engine.get_options())["device_loop"] == 1.0
+    runs = []
     for src in dev.sample_roots(4, seed=3) + [0]:
         a, b = dev.run(src), host.run(src)
         assert np.array_equal(dev.levels(), _oracle(csr, src))
@@ -293,6 +295,8 @@ def test_device_loop_matches_host_loop(rt, mode, predict):
         strip = lambda r: [(l["dir"], l["frontier"], l["frontier_edges"], l["discovered"]) for l in r.levels]
         assert strip(a) == strip(b)
         assert (a.reached, a.edges, a.depth) == (b.reached, b.edges, b.depth)
+        runs.append(a)
+    chain_plans.check("cpu", chain_plans.key("matches_host_loop", mode, {"device_loop_predict": predict}), runs)
 
 
 def test_host_loop_stats_mailbox():
@@ -424,15 +428,17 @@ def test_device_loop_several_ranks(P, mode, predict):
             a, b = dev.run(s), host.run(s)
             strip = lambda r: [(l["dir"], l["frontier"], l["frontier_edges"], l["discovered"]) for l in r.levels]
             out.append((dev.levels(), host.levels(), strip(a), strip(b), (a.reached, a.edges, a.depth),
-                        (b.reached, b.edges, b.depth)))
+                        (b.reached, b.edges, b.depth), chain_plans.summary(a)))
         return out
 
-    for rank_out in run_virtual_ranks(P, body, device="cpu"):
-        for (ld, lh, ra, rb, ta, tb), s in zip(rank_out, srcs):
+    for rank, rank_out in enumerate(run_virtual_ranks(P, body, device="cpu")):
+        for (ld, lh, ra, rb, ta, tb, _), s in zip(rank_out, srcs):
             assert np.array_equal(ld, _oracle(csr, s)) and np.array_equal(lh, ld)
             # (the device loop stops once every vertex with an edge is reached:
             # the host loop's extra last level expanded its frontier for nothing)
             assert ra == rb[:len(ra)] and all(r[3] == 0 for r in rb[len(ra):]) and ta == tb
+        chain_plans.check("cpu", chain_plans.key("several_ranks", P, mode, {"device_loop_predict": predict}, "rank", rank),
+                          [o[-1] for o in rank_out])
 
 
 @pytest.mark.parametrize("knobs", [
@@ -466,13 +472,15 @@ def test_device_loop_sparse_lists_several_ranks(P, knobs):
             a, b = dev.run(s), host.run(s)
             strip = lambda r: [(l["dir"], l["frontier"], l["frontier_edges"], l["discovered"]) for l in r.levels]
             out.append((dev.levels(), strip(a), strip(b), (a.reached, a.edges, a.depth), (b.reached, b.edges, b.depth),
-                        a.mispredicts, [c[1] for c in a.chains]))
+                        a.mispredicts, [c[1] for c in a.chains], chain_plans.summary(a)))
         return out
 
-    for rank_out in run_virtual_ranks(P, body, device="cpu"):
+    for rank, rank_out in enumerate(run_virtual_ranks(P, body, device="cpu")):
+        chain_plans.check("cpu", chain_plans.key("sparse_lists_several_ranks", P, knobs, "rank", rank),
+                          [o[-1] for o in rank_out])
         mis = 0
         forms = ""
-        for (ld, ra, rb, ta, tb, m, fs), s in zip(rank_out, srcs):
+        for (ld, ra, rb, ta, tb, m, fs, _), s in zip(rank_out, srcs):
             assert np.array_equal(ld, _oracle(csr, s))
             # (the device loop stops once every vertex with an edge is reached)
             assert ra == rb[:len(ra)] and all(r[3] == 0 for r in rb[len(ra):]) and ta == tb

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import chain_plans
 import distributed_cuda_bfs_amd as dbfs
 from distributed_cuda_bfs_amd.parallel.runtime import init_runtime, run_virtual_ranks
 
@@ -384,6 +385,7 @@ def test_device_loop_matches_host_loop_gpu(gpu_runtime, mode, byte_edges):
     for b in (dev, host):
         b.engine.set_heuristics(24.0, 24.0, 8, td_byte_edges=byte_edges)
         b.engine.phase_timing = True
+    runs = []
     for src in dev.sample_roots(4, seed=5):
         a = dev.run(src)
         exp = dbfs.cpu_bfs(csr, src)[0]
@@ -393,6 +395,8 @@ def test_device_loop_matches_host_loop_gpu(gpu_runtime, mode, byte_edges):
         assert strip(a) == strip(r)
         assert (a.reached, a.edges, a.depth) == (r.reached, r.edges, r.depth)
         assert all(l["ms"] > 0 for l in a.levels)
+        runs.append(a)
+    chain_plans.check("gpu", chain_plans.key("matches_host_loop", mode, {"td_byte_edges": byte_edges}), runs)
 
 
 @pytest.mark.parametrize("lane_limit", [1, 8, 64])
@@ -695,10 +699,13 @@ def test_device_loop_several_ranks_gpu(gpu_runtime, mode):
     dev.engine.set_option("td_byte_edges", 1 << 12)
     host = dbfs.BFS(p, rt, mode=mode, force_exchange=True)
     host.engine.set_option("device_loop", 0)
+    runs = []
     for src in dev.sample_roots(3, seed=12):
         a, b = dev.run(src), host.run(src)
         assert np.array_equal(dev.levels(), dbfs.cpu_bfs(csr, src)[0])
         assert strip(a) == strip(b) and (a.reached, a.edges, a.depth) == (b.reached, b.edges, b.depth)
+        runs.append(a)
+    chain_plans.check("gpu", chain_plans.key("several_ranks", mode, "forced_exchange"), runs)
     comm.barrier()
 
     srcs = [5, 1234]
@@ -709,12 +716,13 @@ def test_device_loop_several_ranks_gpu(gpu_runtime, mode):
         out = []
         for s in srcs:
             x, y = d.run(s), h.run(s)
-            out.append((d.levels(), strip(x) == strip(y)))
+            out.append((d.levels(), strip(x) == strip(y), chain_plans.summary(x)))
         return out
 
-    for rank_out in run_virtual_ranks(3, body, device="hip"):
-        for (lv, same), s in zip(rank_out, srcs):
+    for rank, rank_out in enumerate(run_virtual_ranks(3, body, device="hip")):
+        for (lv, same, _), s in zip(rank_out, srcs):
             assert same and np.array_equal(lv, dbfs.cpu_bfs(csr, s)[0])
+        chain_plans.check("gpu", chain_plans.key("several_ranks", mode, "rank", rank), [o[-1] for o in rank_out])
 
 
 @pytest.mark.parametrize("mode,sparse_edges", [("bu", 0), ("td", 0), ("td", 1 << 16), ("do", 1 << 16)])

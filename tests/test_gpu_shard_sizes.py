@@ -31,6 +31,7 @@ device-side validation.  Everything is an integer: no tolerance.
 import numpy as np
 import pytest
 
+import chain_plans
 import distributed_cuda_bfs_amd as dbfs
 from distributed_cuda_bfs_amd.parallel.runtime import run_virtual_ranks
 from test_gpu_engine import _describe
@@ -161,7 +162,9 @@ def run_case(g, mode, options, roots=None, max_hubs=None):
         bfs.mode = mode
         for k, v in options.items():
             bfs.engine.set_option(k, v)
-        return [check_run(g, bfs, s) for s in (roots or g.roots[:2])]
+        res = [check_run(g, bfs, s) for s in (roots or g.roots[:2])]
+        chain_plans.check("gpu", chain_plans.key("shard", g.name, mode, options, roots or "-", max_hubs), res)
+        return res
     finally:
         g.restore()
 
