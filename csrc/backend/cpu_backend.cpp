@@ -529,6 +529,24 @@ class CpuBackend final : public Backend {
       a.frontier[w] = nb[w];
       a.visited[w] |= nb[w];
     }
+    // the apply's settle and finish: the claimed words are the new frontier
+    // (an update with force over them: levels, unit statistics, the fused
+    // finish with its folded scan)
+    UpdateArgs u;
+    u.g = a.g;
+    u.cand = a.frontier;
+    u.force = true;
+    u.visited = a.visited;
+    u.frontier = a.frontier;
+    u.out = a.out;
+    u.words = a.words;
+    u.unit_cnt = a.unit_cnt;
+    u.unit_deg = a.unit_deg;
+    u.guard = a.guard;
+    u.fuse_scan = true;
+    u.fold_scan = a.fin.fold_scan;
+    u.scan = a.fin.scan;
+    update_frontier(u);
   }
 
   void level_finish(const LevelFinishArgs& a) override {

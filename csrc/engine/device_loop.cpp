@@ -123,7 +123,10 @@ class DeviceLoop {
   int bin_shift_ = 12;
   int64_t nbins_ = 0;
   bool binned_ = false;
-  static constexpr int kBinGrid = 1024;
+  // workgroups of a binned level's count / fill passes: all resident (two
+  // 512-thread workgroups per CU on 256 CUs), each a persistent owner of its
+  // part of every bin (td_kernels.hip: 512 / 1024 measured equal, 256 slower)
+  static constexpr int kBinGrid = 512;
   int64_t td_grid_ = 1, td_grid_filter_ = 1;
   bool seed_gather_ = false;
   uint64_t late_ticks_ = 0;  // DBFS_FAULT_INJECT=kind=late_wg (TdSparseArgs::late_ticks)
@@ -215,6 +218,7 @@ class DeviceLoop {
   void emit_binned(Chain& c);
   void emit_dense(Chain& c);
   void emit_bottom_up(Chain& c);
+  FusedFinishArgs fused_finish(Chain& c);
   void fuse_update(Chain& c, UpdateArgs& tu);
 
   RunResult collect(int nlev, std::chrono::steady_clock::time_point t1);
@@ -838,8 +842,8 @@ void DeviceLoop::emit_sparse(Chain& c) {
 }
 
 // 'X': binned top-down (one rank): targets binned by vertex range, claimed
-// per bin in LDS; a sparse level (or the seed) handed over the work list,
-// else compact.
+// per bin in LDS, settled and the level ended by the same apply kernel; a
+// sparse level (or the seed) handed over the work list, else compact.
 void DeviceLoop::emit_binned(Chain& c) {
   const LevelPlan& p = c.p;
   const int L = p.level;
@@ -859,36 +863,42 @@ void DeviceLoop::emit_binned(Chain& c) {
   xa.visited = e_.visited_.data() + me_ * W_;
   xa.frontier = fr_own(p.cur ^ 1);
   xa.words = W_;
+  // the apply settles the new frontier (levels, unit statistics) and ends the
+  // level in its last workgroup: no update, no scan launch
+  xa.out = e_.level_out(L + 1);
+  xa.unit_cnt = e_.unit_cnt_.data();
+  xa.unit_deg = e_.unit_deg_.data();
+  xa.fin = fused_finish(c);
   be_.td_binned(xa);
-  // levels and unit statistics of the new frontier (already claimed)
-  UpdateArgs tu = ua_;
-  tu.cand = fr_own(p.cur ^ 1);
-  tu.cand_bytes = nullptr;
-  tu.nchunks = 1;
-  tu.clear_cand = false;
-  tu.force = true;
-  tu.frontier = fr_own(p.cur ^ 1);
-  tu.out.new_level = L + 1;
-  tu.guard = c.guard;
-  be_.update_frontier(tu);
 }
 
-// The update's fused finish: the level's totals (and with one rank its
-// decision) in its last workgroup, as bottom-up -- per-workgroup totals slots
-// and a two-level ticket, no scan launch unless a compaction follows.
+// A settling kernel's fused finish (the update's, the binned apply's): the
+// level's totals (and with one rank its decision) in its last workgroup, as
+// bottom-up -- per-workgroup totals slots and a two-level ticket, no scan
+// launch unless a compaction follows.
 // RMAT-26 1344 / 1341 -> 1363 / 1353 GTEPS; top-down only equal within noise.
 // (A first version with one workgroup per 4 units and totals atomics on one
 // address: level 1 of RMAT-26 38 -> 117 us.)
-void DeviceLoop::fuse_update(Chain& c, UpdateArgs& tu) {
-  tu.fuse_scan = true;
-  tu.scan = scan_args(c.p.level, c.guard);
+FusedFinishArgs DeviceLoop::fused_finish(Chain& c) {
+  FusedFinishArgs f;
+  f.scan = scan_args(c.p.level, c.guard);
   // graphs of at most kFoldScanUnits units: the next compaction's unit
   // prefixes too (one scan_units launch less per dense level)
-  tu.fold_scan = e_.nunits_ <= kFoldScanUnits;
-  c.folded = tu.fold_scan;
-  tu.tot = scratch(e_.td_tot_, static_cast<size_t>(2 * kMaxFusedGrid + 2 * kFusedGroups), false);
-  tu.group_ticket = group_tickets();
+  f.fold_scan = e_.nunits_ <= kFoldScanUnits;
+  c.folded = f.fold_scan;
+  f.tot = scratch(e_.td_tot_, static_cast<size_t>(2 * kMaxFusedGrid + 2 * kFusedGroups), false);
+  f.group_ticket = group_tickets();
   c.fused_scan = true;
+  return f;
+}
+
+void DeviceLoop::fuse_update(Chain& c, UpdateArgs& tu) {
+  const FusedFinishArgs f = fused_finish(c);
+  tu.fuse_scan = true;
+  tu.scan = f.scan;
+  tu.fold_scan = f.fold_scan;
+  tu.tot = f.tot;
+  tu.group_ticket = f.group_ticket;
 }
 
 // 'T': a dense top-down level -- compact (unless a sparse level or the seed

@@ -374,6 +374,16 @@ struct ScanArgs {
   bool finish = true;
 };
 
+// The fused finish of a kernel that settles a level's new frontier (the
+// update, the binned apply), as DeviceLoop::fused_finish builds it: what
+// UpdateArgs::fold_scan / scan / tot / group_ticket describe.
+struct FusedFinishArgs {
+  bool fold_scan = false;
+  ScanArgs scan;
+  int64_t* tot = nullptr;
+  unsigned* group_ticket = nullptr;
+};
+
 // Device loop, several ranks: after the totals' all-reduce (stats[2..3] =
 // global count / degree sum), one thread runs level_ctrl_finish (seed: from
 // ctrl_init) and stamps rec / the mailbox, as the one-rank scan does.
@@ -602,14 +612,19 @@ struct TdSparseArgs {
 // Binned top-down level (one rank, large frontiers; propagation blocking):
 // instead of a random probe and a random store per frontier edge, the edges'
 // targets are first written into nbins contiguous bins by target range
-// (count pass: per-workgroup bin counts; scan; fill pass: each workgroup
-// writes its targets at its scanned positions), then one workgroup per bin
+// (count pass: per-workgroup bin counts; scan; fill pass: each workgroup puts
+// a step's targets in bin order in LDS and copies every bin's run out
+// contiguously at its scanned position), then one workgroup per bin
 // holds the bin's slice of `visited` in LDS, claims the unvisited targets with
 // LDS atomics and writes the bin's frontier / visited words, the new
 // vertices' levels and its units' statistics -- every random access of the
-// level lands in one bin's LDS / L2-resident range.  Replaces td_expand; an
-// update_frontier with force = true over the new frontier (cand = frontier)
-// then writes the levels and unit statistics.  Correct for any frontier size.
+// level lands in one bin's LDS / L2-resident range.  Replaces td_expand AND
+// the update: a bin is a whole number of 4096-vertex units (shift >= 12), so
+// the apply workgroup settles its units from the words it holds in LDS (as
+// update_unit does from the candidate words) and the level ends in the
+// apply's last workgroup (the update's fused finish: totals slots, two-level
+// ticket, scan_finish, the folded unit scan).  No launch follows the apply.
+// Correct for any frontier size.
 struct BinArgs {
   ShardView g;
   WorkListIn in;
@@ -631,6 +646,16 @@ struct BinArgs {
   word_t* visited = nullptr;
   word_t* frontier = nullptr;          // next frontier (every word written)
   int64_t words = 0;
+  // the apply's settle (as UpdateArgs): the new vertices' levels, every
+  // unit's statistics (count / degree sum of its new vertices with a
+  // non-empty row) ...
+  LevelOut out;
+  int64_t* unit_cnt = nullptr;         // nunits
+  int64_t* unit_deg = nullptr;
+  // ... and the level's end in its last workgroup (UpdateArgs::fuse_scan /
+  // fold_scan / tot / group_ticket: required; the apply's grid is nbins <=
+  // kBinMaxBins <= kMaxFusedGrid workgroups and every one takes the ticket)
+  FusedFinishArgs fin;
 };
 // Largest bin span (vertices) and bin count the kernels support.
 constexpr int kBinMaxShift = 18;
@@ -755,6 +780,7 @@ constexpr int kBuQueueStride = 32;
 // Fused update finish, two-level ticket (UpdateArgs::group_ticket).
 constexpr int kFusedGroup = 64;
 constexpr int kFusedGroups = kMaxFusedGrid / kFusedGroup;
+static_assert(kBinMaxBins <= kMaxFusedGrid, "the binned apply's workgroups each own a totals slot");
 
 struct BuArgs {
   ShardView g;

@@ -199,7 +199,8 @@ struct EngineOptions {
   int64_t td_direct_edges = int64_t(1) << 16;
   // Device loop, one rank: top-down levels predicted to have at least this
   // many frontier edges run binned (BinArgs: targets binned by vertex range,
-  // claimed per bin in LDS) instead of td_expand + update; 0 disables.  Only
+  // claimed per bin in LDS, settled and the level ended by the same apply
+  // kernel) instead of td_expand + update; 0 disables.  Only
   // on graphs of at least td_bin_min_rows vertices (level bytes and visited
   // bits far past the L2: a direct level's two random lines per edge go to
   // HBM; below, the direct level is faster -- RMAT-22 top-down) and only
@@ -218,8 +219,9 @@ struct EngineOptions {
   int64_t td_bin_min_rows = int64_t(1) << 26;
   // ... about 2^td_bin_log2_bins bins (of >= 4096 vertices, at most
   // kBinMaxBins; each bin's visited slice must fit LDS).  RMAT-26, the 28 M-edge
-  // binned level: 256 / 512 / 1024 bins 407 / 417 / 441 us (more bins: the
-  // fill pass scatters into more open lines).
+  // binned level: 256 / 512 / 1024 bins 407 / 417 / 441 us with the scatter
+  // fill (more bins: more open lines); with the staged fill 256 / 512 bins
+  // 340 / 357 us (profiles/binned_settle_fill_sweep.txt).
   static constexpr int64_t td_bin_log2_bins = 8;
   // Dense top-down levels predicted at >= td_unvis_edges frontier edges that
   // start with >= td_unvis_vis_frac of the adjacency visited test targets in

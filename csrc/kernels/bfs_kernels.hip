@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "kernel_common.hpp"
+#include "settle_device.hpp"
 #include "launch.hpp"
 #include "level_device.hpp"
 #include "wave.hpp"
@@ -239,98 +240,6 @@ __device__ __forceinline__ word_t gather_level_bits(const uint8_t* p, uint8_t lv
   return bits;
 }
 
-// A unit's statistics; write-through when the fused finish's last workgroup
-// scans them (UpdateArgs::fold_scan: read there with agent-scope loads).
-__device__ __forceinline__ void store_unit_stats(const UpdateArgs& a, int64_t unit, long long c, long long d) {
-  if (a.fold_scan) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.unit_cnt + unit), static_cast<unsigned long long>(c),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.unit_deg + unit), static_cast<unsigned long long>(d),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    a.unit_cnt[unit] = c;
-    a.unit_deg[unit] = d;
-  }
-}
-
-// The fused finish's unit prefixes (UpdateArgs::fold_scan; every thread of the
-// last workgroup of kBlock threads): unit_cnt / unit_deg become the exclusive
-// prefixes over all units (at most kFoldScanUnits) and the chunk prefixes
-// part_cnt / part_deg zero -- what scan_units_kernel leaves for the
-// compaction.  The units are spread over all kBlock threads (a run of
-// ceil(nunits / kBlock) each) and a run's agent-scope loads go out kFoldRun at
-// a time: each batch is one round trip to memory (the stats were stored
-// write-through by other XCDs' waves), so a run of up to kFoldRun units -- 2048
-// units, a 2^23-vertex shard -- costs one round trip, its values kept in
-// registers for the second pass.  (The first version gave each thread a run of
-// kFoldScanUnits / kBlock units, four loads in flight: on a 2048-unit shard one
-// wave made 16 dependent round trips -- the P = 8 post-bottom-up update 39.4 ->
-// 33.8 us, RMAT-22 top-down only +2 %, profiles/r5_fold_scan_ab.txt.)
-__device__ __forceinline__ long long agent_load_i64(const int64_t* p) {
-  return static_cast<long long>(
-      __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-constexpr int kFoldRun = 8;
-__device__ __forceinline__ void fold_unit_scan(const ScanArgs& a) {
-  __shared__ long long s_fc[kBlock / kWave], s_fd[kBlock / kWave];
-  const int t = threadIdx.x, lane = lane_id(), wv = t >> 6;
-  const int64_t n = a.nunits;
-  const int64_t per = (n + kBlock - 1) / kBlock;
-  const int64_t u0 = min(static_cast<int64_t>(t) * per, n);
-  const int64_t u1 = min(u0 + per, n);
-  long long c[kFoldRun], d[kFoldRun];
-  long long sc = 0, sd = 0;
-  for (int64_t b = u0; b < u1; b += kFoldRun) {
-#pragma unroll
-    for (int k = 0; k < kFoldRun; ++k) {
-      const bool in = b + k < u1;
-      c[k] = in ? agent_load_i64(a.unit_cnt + b + k) : 0ll;
-      d[k] = in ? agent_load_i64(a.unit_deg + b + k) : 0ll;
-    }
-#pragma unroll
-    for (int k = 0; k < kFoldRun; ++k) {
-      sc += c[k];
-      sd += d[k];
-    }
-  }
-  const long long ic = wave_incl_scan(sc), id = wave_incl_scan(sd);
-  __syncthreads();  // (s_fc / s_fd: the caller's earlier LDS use is done)
-  if (lane == kWave - 1) {
-    s_fc[wv] = ic;
-    s_fd[wv] = id;
-  }
-  __syncthreads();
-  long long oc = ic - sc, od = id - sd;
-  for (int k = 0; k < wv; ++k) {
-    oc += s_fc[k];
-    od += s_fd[k];
-  }
-  for (int64_t b = u0; b < u1; b += kFoldRun) {
-    if (per > kFoldRun) {
-      // (a longer run: the batch again -- the registers hold the last one)
-#pragma unroll
-      for (int k = 0; k < kFoldRun; ++k) {
-        const bool in = b + k < u1;
-        c[k] = in ? agent_load_i64(a.unit_cnt + b + k) : 0ll;
-        d[k] = in ? agent_load_i64(a.unit_deg + b + k) : 0ll;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kFoldRun; ++k) {
-      if (b + k < u1) {
-        a.unit_cnt[b + k] = oc;
-        a.unit_deg[b + k] = od;
-      }
-      oc += c[k];
-      od += d[k];
-    }
-  }
-  for (int64_t p = t; p * kScanChunk < a.nunits; p += kBlock) {
-    a.part_cnt[p] = 0;
-    a.part_deg[p] = 0;
-  }
-}
-
 // One wave per 64-word unit, kUnitsPerBlock units per workgroup; with the
 // fused finish a smaller grid strides over the units (fewer ticket arrivals).
 // kSplit waves per unit (small graphs: 4, each over 16 of its words -- a
@@ -366,30 +275,9 @@ __device__ __forceinline__ void update_unit(const UpdateArgs& a, int64_t unit, b
     }
     if (a.clear_cand && c && !use_bytes) a.cand[wl] = 0;
   }
-  // New vertices of the unit, 64 per step (one per lane, whatever word they
-  // sit in): a sparse level has about one new vertex per word, and one word
-  // per step would cost a dependent row_off round trip per new vertex.
-  cnt = 0;
-  deg = 0;
-  const int incl = static_cast<int>(wave_incl_scan(__popcll(nb)));
-  const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
-  const eid_t* __restrict__ ro = a.g.row_off;
-  for (int base = 0; base < total; base += kWave) {
-    const int idx = base + lane;
-    const int pos = wave_set_position(nb, incl, idx);
-    if (idx < total) {
-      const int64_t v = w0 * 64 + pos;
-      if (!(use_bytes && a.level_direct)) a.out.store(v);
-      const eid_t d = ro[v + 1] - ro[v];
-      if (d > 0) {
-        cnt += 1;
-        deg += d;
-      }
-    }
-  }
-  cnt = wave_sum(cnt);
-  deg = wave_sum(deg);
-  if (kSplit == 1 && lane == 0) store_unit_stats(a, unit, cnt, deg);
+  // (the unit's new vertices 64 per step, whatever word they sit in)
+  settle_new_vertices(a.g.row_off, a.out, !(use_bytes && a.level_direct), w0 * 64, nb, cnt, deg);
+  if (kSplit == 1 && lane == 0) store_unit_stats(a.unit_cnt, a.unit_deg, a.fold_scan, unit, cnt, deg);
 }
 
 // A unit per workgroup, its kSplit (= kUnitsPerBlock) waves each over a part
@@ -411,7 +299,7 @@ __device__ __forceinline__ void update_unit_split(const UpdateArgs& a, int64_t u
       c += s_pc[k];
       d += s_pd[k];
     }
-    store_unit_stats(a, unit, c, d);
+    store_unit_stats(a.unit_cnt, a.unit_deg, a.fold_scan, unit, c, d);
   }
   __syncthreads();  // (s_pc / s_pd reused by the next unit)
 }
@@ -448,8 +336,6 @@ __global__ __launch_bounds__(kBlock) void update_kernel(UpdateArgs a) {
   // fused finish (as the whole-unit bottom-up kernel's): raw unit statistics,
   // the workgroup's totals in its slot of tot, a ticket; the last workgroup
   // sums the slots and finishes the level
-  __shared__ long long s_c[kUnitsPerBlock], s_d[kUnitsPerBlock];
-  __shared__ int s_last, s_level_last;  // (separate: waves read s_last while wave 0 decides the level)
   long long wc = 0, wd = 0;
   if constexpr (kSplit) {
     for (int64_t unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
@@ -467,103 +353,14 @@ __global__ __launch_bounds__(kBlock) void update_kernel(UpdateArgs a) {
       wd += deg;
     }
   }
-  if (lane_id() == 0) {
-    s_c[wv] = wc;
-    s_d[wv] = wd;
-  }
   // (pushed words: every wave's write-through stores drained before the
-  // ticket, so the level end published after it covers them; likewise the
-  // unit statistics the last workgroup scans with fold_scan -- stored by
-  // lane 0 of every wave, and a barrier does not wait for another wave's
-  // stores)
+  // ticket, so the level end published after it covers them)
   if constexpr (kRanks)
     if (a.push) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (a.fold_scan) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    long long c = 0, d = 0;
-#pragma unroll
-    for (int k = 0; k < kUnitsPerBlock; ++k) {
-      c += s_c[k];
-      d += s_d[k];
-    }
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.tot + 2 * blockIdx.x), static_cast<unsigned long long>(c),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.tot + 2 * blockIdx.x + 1),
-                       static_cast<unsigned long long>(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // the group's last workgroup sums the group (below), then takes the
-    // level ticket
-    const unsigned grp = blockIdx.x / kFusedGroup;
-    const unsigned gsz = min(static_cast<unsigned>(kFusedGroup), gridDim.x - grp * kFusedGroup);
-    const unsigned prev = atomicAdd(a.group_ticket + grp * kBuQueueStride, 1u);
-    s_last = prev == gsz - 1;
-    if (s_last) {
-      atomicExch(a.group_ticket + grp * kBuQueueStride, 0u);
-      last_arriver_acquire();
-    }
-  }
-  __syncthreads();
-  if (!s_last) return;
-  auto slot_sum = [&](const int64_t* slots, unsigned first, unsigned n, long long& c, long long& d) {
-    c = 0;
-    d = 0;
-    for (unsigned g = threadIdx.x; g < n; g += kBlock) {
-      c += static_cast<long long>(__hip_atomic_load(reinterpret_cast<const unsigned long long*>(slots + 2 * (first + g)),
-                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      d += static_cast<long long>(__hip_atomic_load(
-          reinterpret_cast<const unsigned long long*>(slots + 2 * (first + g) + 1), __ATOMIC_RELAXED,
-          __HIP_MEMORY_SCOPE_AGENT));
-    }
-  };
-  long long c = 0, d = 0;
-  // group total (kFusedGroup slots: the first wave), then the level ticket
-  const unsigned grp = blockIdx.x / kFusedGroup;
-  const unsigned ngroups = (gridDim.x + kFusedGroup - 1) / kFusedGroup;
-  if (wv == 0) {
-    slot_sum(a.tot, grp * kFusedGroup, min(static_cast<unsigned>(kFusedGroup), gridDim.x - grp * kFusedGroup), c, d);
-    c = wave_sum(c);
-    d = wave_sum(d);
-    if (lane_id() == 0) {
-      int64_t* gt = a.tot + 2 * kMaxFusedGrid;
-      __hip_atomic_store(reinterpret_cast<unsigned long long*>(gt + 2 * grp), static_cast<unsigned long long>(c),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(reinterpret_cast<unsigned long long*>(gt + 2 * grp + 1), static_cast<unsigned long long>(d),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned prev = atomicAdd(a.scan.ticket, 1u);
-      s_level_last = prev == ngroups - 1;
-      if (s_level_last) last_arriver_acquire();
-    }
-  }
-  __syncthreads();
-  if (!s_level_last) return;
-  slot_sum(a.tot + 2 * kMaxFusedGrid, 0, ngroups, c, d);
-  c = wave_sum(c);
-  d = wave_sum(d);
-  __syncthreads();  // (s_c / s_d reused)
-  if (lane_id() == 0) {
-    s_c[wv] = c;
-    s_d[wv] = d;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    long long tc = 0, td = 0;
-#pragma unroll
-    for (int k = 0; k < kUnitsPerBlock; ++k) {
-      tc += s_c[k];
-      td += s_d[k];
-    }
-    scan_finish(a.scan, tc, td);
-    s_c[0] = tc;
-    s_d[0] = td;
-  }
-  if (a.fold_scan) fold_unit_scan(a.scan);
+  long long tc = 0, td = 0;
+  if (!fused_finish<kBlock>(a.tot, a.group_ticket, a.scan, a.fold_scan, wc, wd, tc, td)) return;
   if constexpr (kRanks) {
-    if (a.end.active) {
-      __syncthreads();
-      direct_level_end(a.end, s_c[0], s_d[0], a.scan.stats, a.fin, s_x);
-    }
+    if (a.end.active) direct_level_end(a.end, tc, td, a.scan.stats, a.fin, s_x);
   }
 }
 

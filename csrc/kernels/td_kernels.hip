@@ -15,6 +15,7 @@
 #include "kernel_common.hpp"
 #include "launch.hpp"
 #include "level_device.hpp"
+#include "settle_device.hpp"
 #include "wave.hpp"
 
 namespace dbfs {
@@ -991,60 +992,92 @@ __global__ __launch_bounds__(kBlock) void td_sparse_bits_kernel(TdSparseArgs a) 
 
 
 // ---------------------------------------------------------------------------
-// Binned top-down level (BinArgs).  Count and fill passes walk the same edge
-// blocks per workgroup (b = blockIdx.x, += gridDim.x) with the td_expand owner
-// map; a workgroup's targets of bin k land at bin_start[k] + wg_off[k * grid +
-// g] plus an LDS slot.  1024-thread workgroups, 2 edges per thread per block.
-constexpr int kBinThreads = 1024;
+// Binned top-down level (BinArgs).  Count and fill passes walk the same steps
+// per workgroup (b = blockIdx.x, += gridDim.x; a step is kBinSpan edge blocks)
+// with the td_expand owner map; a workgroup's targets of bin k land at
+// bin_start[k] + wg_off[k * grid + g] onwards, in the order of its steps.
+//   * Run-aware slots: a wave's lanes hold consecutive entries of the step,
+//     and within a row the bin index never decreases (rows are in
+//     neighbour-id order: exactly up to 4096 entries, by id buckets that never
+//     straddle a bin beyond, graph_sort.hip), so a lane whose bin differs from
+//     its left neighbour's starts a run; the run's first lane issues ONE LDS
+//     add of the run's length and every other lane's slot is its distance to
+//     that lane -- one round per item whatever the number of runs (a row
+//     boundary inside the wave simply starts another run, possibly of a bin
+//     seen before: two adds on one counter).  (Before: up to 4 serial rounds
+//     of leader election with a returning LDS atomic each, then one per lane.)
+//   * Contiguous stores: the fill puts a step's targets in bin order in LDS
+//     (position = the bin's offset in the step, from an exclusive scan of the
+//     step's bin counts, + the slot) and copies them out in that order, so
+//     consecutive lanes store consecutive words of a bin's region (4096 edges
+//     per step over 256 bins: 64-B runs on average, whole lines for the
+//     popular bins) -- before, 256 threads each appended 4 bytes to a region
+//     of its own choice, and the 1024 x 256 regions' partly written lines did
+//     not fit the L2 next to the col stream.
+//   * The owner map's bases and the bin positions in 32 bits (kBase32: at
+//     most 2^32 adjacency entries), the owners in 16: 64 KiB of LDS for the
+//     fill, two 512-thread workgroups per CU, the grid (512) all resident.
+// Measured on RMAT-26 (profiles/binned_settle_fill_sweep.txt), the 28 M-edge
+// level / the 2.9 M-edge one: scatter, grid 1024 403 / 103 us (grid 512 459 /
+// 111, grid 256 671 / 131: fewer open lines alone lose more in occupancy);
+// staged 512 threads x 4096 edges, grid 512 340 / 93 (grid 1024 338 / 97, grid
+// 256 439 / 98); staged 1024 x 8192, grid 256 354 / 95; 512 bins 357 / 101.
+constexpr int kBinThreads = 1024;     // the apply's
 constexpr int kAggRounds = 4;
+constexpr int kBinPassThreads = 512;  // the count / fill passes'
+constexpr int kBinSpan = 2;
 
-// slot = atomicAdd(&cnt[key], 1) for every active lane, with the lanes that
-// share a key served by one LDS atomic (rows in id order put runs of targets
-// in one bin, and 64 same-address LDS atomics serialise): up to kAggRounds
-// distinct keys per wave aggregated, the rest per lane.  Wave-uniform call.
-__device__ __forceinline__ unsigned lds_slot_add(unsigned* cnt, int key, bool active) {
+// The run of equal-bin lanes this lane belongs to (active lanes are a prefix
+// of the wave): head = the run's first lane, len = its lanes.  Wave-uniform
+// call; an inactive lane gets head = its own lane, len = 0.
+__device__ __forceinline__ void wave_bin_run(int bin, bool act, int& head, int& len) {
   const int lane = lane_id();
-  unsigned long long pending = __ballot(active);
-  unsigned slot = 0;
-#pragma unroll
-  for (int r = 0; r < kAggRounds; ++r) {
-    if (!pending) break;
-    const int leader = __ffsll(static_cast<long long>(pending)) - 1;
-    const int k = __shfl(key, leader, kWave);
-    const unsigned long long m = __ballot(active && key == k) & pending;
-    unsigned base = 0;
-    if (lane == leader) base = atomicAdd(&cnt[k], static_cast<unsigned>(__popcll(m)));
-    base = __shfl(base, leader, kWave);
-    if ((m >> lane) & 1ull) slot = base + mask_rank(m);
-    pending &= ~m;
+  const int left = __shfl_up(bin, 1, kWave);
+  const unsigned long long acts = __ballot(act);
+  const unsigned long long heads = __ballot(act && (lane == 0 || left != bin));
+  head = lane;
+  len = 0;
+  if (act) {
+    head = 63 - __clzll(static_cast<long long>(heads & (~0ull >> (63 - lane))));  // (bit 0 is set: lane 0 is active)
+    const unsigned long long above = head == 63 ? 0ull : heads & (~0ull << (head + 1));
+    const int end = above ? __ffsll(static_cast<long long>(above)) - 1 : __popcll(acts);
+    len = end - head;
   }
-  if ((pending >> lane) & 1ull) slot = atomicAdd(&cnt[key], 1u);
-  return slot;
 }
 
-template <bool kFill>
-__global__ __launch_bounds__(kTdThreads) void bin_pass_kernel(BinArgs a) {
-  constexpr int kItems = kTdEdgesPerBlock / kTdThreads;
-  __shared__ int32_t s_owner[kTdEdgesPerBlock];
-  __shared__ long long s_base[kTdEdgesPerBlock + 1];
-  __shared__ int32_t s_wmax[kTdThreads / kWave];
-  __shared__ unsigned s_cnt[kBinMaxBins];
-  __shared__ long long s_start[kFill ? kBinMaxBins : 1];
+template <bool kFill, bool kBase32>
+__global__ __launch_bounds__(kBinPassThreads) void bin_pass_kernel(BinArgs a) {
+  constexpr int kThreads = kBinPassThreads, kSpan = kBinSpan;
+  constexpr int kEPB = kSpan * kTdEdgesPerBlock;
+  constexpr int kItems = kEPB / kThreads;
+  constexpr int kWaves = kThreads / kWave;
+  constexpr int kPer = kBinMaxBins / kThreads;  // bins per thread of the scans
+  static_assert(kBinMaxBins % kThreads == 0 && kEPB % kThreads == 0, "bins and edges divide among the threads");
+  using BaseT = std::conditional_t<kBase32, uint32_t, long long>;
+  __shared__ uint16_t s_owner[kEPB];
+  __shared__ BaseT s_base[kEPB + 1];
+  __shared__ int32_t s_wmax[kWaves];
+  __shared__ unsigned s_step[kBinMaxBins];              // count: the workgroup's totals; fill: this step's counts
+  __shared__ unsigned s_off[kFill ? kBinMaxBins : 1];   // the bin's offset in the step's staging order
+  __shared__ BaseT s_pos[kFill ? kBinMaxBins : 1];      // where the workgroup's next target of the bin goes in buf
+  __shared__ vid_t s_stage[kFill ? kEPB : 1];
+  __shared__ long long s_part[kWaves];
+  __shared__ unsigned s_wsum[kWaves];
   if (!a.guard.live()) return;
   const long long q = a.dev_stats[0], m = a.dev_stats[1];
   const int t = threadIdx.x;
+  const int lane = lane_id();
+  const int wv = t >> 6;
   if (!kFill && a.clear_frontier) {
     stamp_level_start(a.guard.ctrl);  // first kernel of the level (no compaction ran)
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kTdThreads + t; i < q;
-         i += static_cast<int64_t>(gridDim.x) * kTdThreads)
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + t; i < q;
+         i += static_cast<int64_t>(gridDim.x) * kThreads)
       a.clear_frontier[a.in.qv[i] >> 6] = 0ull;
   }
-  for (int k = t; k < a.nbins; k += kTdThreads) s_cnt[k] = 0;
+  for (int k = t; k < a.nbins; k += kThreads) s_step[k] = 0;
   if constexpr (kFill) {
-    // bin starts: exclusive scan of the bin totals (<= kBinMaxBins), serial
-    // per wave-chunk then across the 4 waves
-    __shared__ long long s_part[kTdThreads / kWave];
-    constexpr int kPer = kBinMaxBins / kTdThreads;
+    // bin starts: exclusive scan of the bin totals, plus this workgroup's
+    // offset in the bin
     long long c[kPer], sum = 0;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
@@ -1053,44 +1086,105 @@ __global__ __launch_bounds__(kTdThreads) void bin_pass_kernel(BinArgs a) {
       sum += c[k];
     }
     const long long incl = wave_incl_scan(sum);
-    if (lane_id() == kWave - 1) s_part[t >> 6] = incl;
+    if (lane == kWave - 1) s_part[wv] = incl;
     __syncthreads();
     long long off = incl - sum;
-    for (int w = 0; w < (t >> 6); ++w) off += s_part[w];
+    for (int w = 0; w < wv; ++w) off += s_part[w];
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
       const int b = t * kPer + k;
-      if (b < a.nbins) s_start[b] = off + a.cnt[static_cast<int64_t>(b) * a.grid + blockIdx.x];
+      if (b < a.nbins) s_pos[b] = static_cast<BaseT>(off + a.cnt[static_cast<int64_t>(b) * a.grid + blockIdx.x]);
       off += c[k];
     }
   }
-  // (td_block_owner_map starts with a barrier)
+  // (td_block_owner_map starts with a barrier and has more: the zeroed
+  // counters and the positions are visible before the first slot)
   const long long nblocks = (m + kTdEdgesPerBlock - 1) / kTdEdgesPerBlock;
+  const long long nsteps = (nblocks + kSpan - 1) / kSpan;
   const vid_t* __restrict__ col = a.g.col;
-  for (long long b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    const long long e0 = b * kTdEdgesPerBlock;
-    const int cnt = td_block_owner_map<kTdThreads>(a.in.qscan, a.in.qbase, a.in.blk_vstart, b, nblocks, q, m, s_owner,
-                                                   s_base, s_wmax);
+  for (long long b = blockIdx.x; b < nsteps; b += gridDim.x) {
+    const long long e0 = b * kEPB;
+    const int cnt = td_block_owner_map<kThreads, BaseT, kSpan, uint16_t>(a.in.qscan, a.in.qbase, a.in.blk_vstart, b, nblocks,
+                                                                         q, m, s_owner, s_base, s_wmax);
     vid_t v[kItems];
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
-      const int idx = k * kTdThreads + t;
-      v[k] = idx < cnt ? col[e0 + idx + s_base[s_owner[idx]]] : 0u;
+      const int idx = k * kThreads + t;
+      int64_t ci;
+      if constexpr (kBase32)
+        ci = static_cast<uint32_t>(static_cast<uint32_t>(e0 + idx) + s_base[s_owner[idx]]);
+      else
+        ci = e0 + idx + s_base[s_owner[idx]];
+      v[k] = idx < cnt ? col[ci] : 0u;
     }
+    unsigned slot[kItems];
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
-      const bool act = k * kTdThreads + t < cnt;
+      const bool act = k * kThreads + t < cnt;
       const int bin = static_cast<int>(v[k] >> a.shift);
       DBFS_DCHECK(!act || bin < a.nbins, 8, v[k]);
-      const unsigned slot = lds_slot_add(s_cnt, bin, act);
-      if constexpr (kFill) {
-        if (act) a.buf[s_start[bin] + slot] = v[k];
+      int head, len;
+      wave_bin_run(bin, act, head, len);
+      unsigned base = 0;
+      if (act && lane == head) base = atomicAdd(&s_step[bin], static_cast<unsigned>(len));
+      slot[k] = static_cast<unsigned>(__shfl(static_cast<int>(base), head, kWave)) + static_cast<unsigned>(lane - head);
+    }
+    if constexpr (kFill) {
+      __syncthreads();
+      // the step's bins in staging order: exclusive scan of its counts
+      unsigned c[kPer], sum = 0;
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) {
+        const int bb = t * kPer + k;
+        c[k] = bb < a.nbins ? s_step[bb] : 0u;
+        sum += c[k];
+      }
+      const unsigned incl = wave_incl_scan_u32(sum);
+      if (lane == kWave - 1) s_wsum[wv] = incl;
+      __syncthreads();
+      unsigned off = incl - sum;
+      for (int w = 0; w < wv; ++w) off += s_wsum[w];
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) {
+        const int bb = t * kPer + k;
+        if (bb < a.nbins) s_off[bb] = off;
+        off += c[k];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kItems; ++k) {
+        if (k * kThreads + t < cnt) {
+          const unsigned p = s_off[v[k] >> a.shift] + slot[k];
+          DBFS_DCHECK(p < static_cast<unsigned>(cnt), 14, p);  // (the staging position: inside the step)
+          s_stage[p < static_cast<unsigned>(kEPB) ? p : 0u] = v[k];
+        }
+      }
+      __syncthreads();
+      // copy out in staging order: lane p and lane p + 1 of a bin's run store
+      // neighbouring words
+#pragma unroll
+      for (int k = 0; k < kItems; ++k) {
+        const int p = k * kThreads + t;
+        if (p < cnt) {
+          const vid_t x = s_stage[p];
+          const int bin = static_cast<int>(x >> a.shift);
+          const int64_t g = static_cast<int64_t>(s_pos[bin]) + (p - static_cast<int>(s_off[bin]));
+          DBFS_DCHECK(g >= 0 && g < m, 15, g);  // (the run copy's range: inside the level's targets)
+          if (g >= 0 && g < m) a.buf[g] = x;
+        }
+      }
+      __syncthreads();
+      // the workgroup's positions move past the step; its counts restart
+      // (ordered before the next step's slots by the owner map's barriers)
+      for (int k = t; k < a.nbins; k += kThreads) {
+        s_pos[k] += static_cast<BaseT>(s_step[k]);
+        s_step[k] = 0;
       }
     }
   }
   if constexpr (!kFill) {
     __syncthreads();
-    for (int k = t; k < a.nbins; k += kTdThreads) a.cnt[static_cast<int64_t>(k) * a.grid + blockIdx.x] = s_cnt[k];
+    for (int k = t; k < a.nbins; k += kThreads) a.cnt[static_cast<int64_t>(k) * a.grid + blockIdx.x] = s_step[k];
   }
 }
 
@@ -1128,7 +1222,9 @@ __global__ __launch_bounds__(kTdThreads) void bin_scan_kernel(BinArgs a) {
 
 // One workgroup per bin: the bin's visited slice in LDS, claims of the bin's
 // targets with LDS atomics (lanes on one word aggregated; kApplyItems loads
-// in flight per thread), then the bin's frontier / visited words.
+// in flight per thread), then -- from the LDS copies, no second pass over
+// memory -- the bin's frontier / visited words, the new vertices' levels, its
+// units' statistics, and the level's end (fused_finish, as the update's).
 constexpr int kApplyItems = 8;
 
 __global__ __launch_bounds__(kBinThreads) void bin_apply_kernel(BinArgs a) {
@@ -1136,14 +1232,19 @@ __global__ __launch_bounds__(kBinThreads) void bin_apply_kernel(BinArgs a) {
   __shared__ word_t s_vis[kMaxWords];
   __shared__ word_t s_new[kMaxWords];
   __shared__ long long s_part[kBinThreads / kWave];
+  // (uniform over the grid: the control block changes only in this level's
+  // finish, after every workgroup's ticket)
   if (!a.guard.live()) return;
   const int t = threadIdx.x;
   const int lane = lane_id();
   const int64_t bin = blockIdx.x;
   const int64_t span_w = (int64_t(1) << a.shift) / kWordBits;
   const int64_t w0 = bin * span_w;
-  const int nw = static_cast<int>(min<int64_t>(span_w, a.words - w0));
-  if (nw <= 0) return;
+  // (the grid holds the live bins only, nbins = ceil(words / span_w); a bin
+  // past `words` would have no words and no targets, and still takes its
+  // ticket: nothing returns between the guard and the finish)
+  const int nw = static_cast<int>(max<int64_t>(0, min<int64_t>(span_w, a.words - w0)));
+  DBFS_DCHECK(nw > 0, 12, bin);
   // this bin's start: the totals of the bins before it
   long long before = 0;
   for (int64_t b = t; b < bin; b += kBinThreads) before += a.bin_total[b];
@@ -1171,6 +1272,7 @@ __global__ __launch_bounds__(kBinThreads) void bin_apply_kernel(BinArgs a) {
       word_t bit = 0;
       if (v[k] != 0xFFFFFFFFu) {
         const int64_t l = static_cast<int64_t>(v[k]) - vlo;
+        DBFS_DCHECK(l >= 0 && (l >> 6) < nw, 13, v[k]);  // (the fill put it in this bin)
         w = static_cast<int>(l >> 6);
         bit = 1ull << (l & 63);
         if (s_vis[w] & bit) bit = 0;  // visited: nothing to claim
@@ -1193,11 +1295,31 @@ __global__ __launch_bounds__(kBinThreads) void bin_apply_kernel(BinArgs a) {
     }
   }
   __syncthreads();
-  for (int w = t; w < nw; w += kBinThreads) {
-    const word_t nb = s_new[w];
-    a.frontier[w0 + w] = nb;
-    if (nb) a.visited[w0 + w] = s_vis[w] | nb;
+  // Settle: a wave per 64-word unit of the bin (lane l its word l, from LDS),
+  // as update_unit from the candidate words -- the frontier and visited words,
+  // the new vertices' levels and the unit's statistics.
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);  // (wave-uniform)
+  const int bin_units = (nw + kUnitWords - 1) / kUnitWords;
+  const int64_t unit0 = w0 / kUnitWords;  // (shift >= 12: a bin starts a unit)
+  long long wc = 0, wd = 0;
+  for (int u = wv; u < bin_units; u += kBinThreads / kWave) {
+    const int w = u * kUnitWords + lane;
+    word_t nb = 0;
+    if (w < nw) {
+      nb = s_new[w];
+      a.frontier[w0 + w] = nb;
+      if (nb) a.visited[w0 + w] = s_vis[w] | nb;
+    }
+    long long cnt, deg;
+    settle_new_vertices(a.g.row_off, a.out, true, (w0 + static_cast<int64_t>(u) * kUnitWords) * kWordBits, nb, cnt,
+                        deg);
+    if (lane == 0) store_unit_stats(a.unit_cnt, a.unit_deg, a.fin.fold_scan, unit0 + u, cnt, deg);
+    wc += cnt;
+    wd += deg;
   }
+  // the level's end in the last workgroup (every workgroup arrives here)
+  long long tc, td;
+  (void)fused_finish<kBinThreads>(a.fin.tot, a.fin.group_ticket, a.fin.scan, a.fin.fold_scan, wc, wd, tc, td);
 }
 
 // out bit h = visited bit of td_hub_vertex[h]: one wave per hub word.
@@ -1375,9 +1497,19 @@ void td_expand(const TdArgs& a, hipStream_t st) {
 
 void td_binned(const BinArgs& a, hipStream_t st) {
   if (a.nbins <= 0 || a.grid <= 0 || a.nbins > kBinMaxBins) return;
-  bin_pass_kernel<false><<<static_cast<unsigned>(a.grid), kTdThreads, 0, st>>>(a);
+  const int64_t span_w = (int64_t(1) << a.shift) / kWordBits;
+  DBFS_CHECK(a.shift >= 12 && a.shift <= kBinMaxShift && a.nbins == (a.words + span_w - 1) / span_w,
+             "td_binned: the apply's grid must hold exactly the bins of whole units that cover the words");
+  DBFS_CHECK(a.guard.ctrl && a.fin.tot && a.fin.group_ticket && a.fin.scan.ticket && a.unit_cnt && a.unit_deg,
+             "td_binned: the apply ends the level (fused finish required)");
+  DBFS_CHECK(!a.fin.fold_scan || a.fin.scan.nunits <= kFoldScanUnits, "td_binned: folded scan over too many units");
+  const unsigned grid = static_cast<unsigned>(a.grid);
+  const bool b32 = a.g.nnz <= (int64_t(1) << 32);
+  if (b32) bin_pass_kernel<false, true><<<grid, kBinPassThreads, 0, st>>>(a);
+  else bin_pass_kernel<false, false><<<grid, kBinPassThreads, 0, st>>>(a);
   bin_scan_kernel<<<static_cast<unsigned>(a.nbins), kTdThreads, 0, st>>>(a);
-  bin_pass_kernel<true><<<static_cast<unsigned>(a.grid), kTdThreads, 0, st>>>(a);
+  if (b32) bin_pass_kernel<true, true><<<grid, kBinPassThreads, 0, st>>>(a);
+  else bin_pass_kernel<true, false><<<grid, kBinPassThreads, 0, st>>>(a);
   bin_apply_kernel<<<static_cast<unsigned>(a.nbins), kBinThreads, 0, st>>>(a);
 }
 
