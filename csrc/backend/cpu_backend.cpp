@@ -344,22 +344,69 @@ class CpuBackend final : public Backend {
     }
   }
   // ---- path counts and dependencies (backend.hpp MsBcArgs): plain loops, every
-  // sum in the kernels' order (stored row order per source, the lanes' tree) ----
-  static double bc_row_sum(const MsBcArgs& a, int64_t r, int s, int want) {
-    double sum = 0.0;
+  // sum in the kernels' order (stored row order per source, the lanes' tree).
+  // The two value forms: doubles, and dbfs/wide.hpp's mantissa and exponent ----
+  struct BcF64 {
+    using Sum = double;
+    static Sum sum_zero() { return 0.0; }
+    static void add(Sum& sum, const MsBcArgs& a, int64_t w, int s) { sum += a.val[w * kMsSources + s]; }
+    static void init(const MsBcArgs& a, int s, int64_t src) {
+      for (int64_t v = 0; v < a.m.lvl_rows; ++v) a.val[v * kMsSources + s] = v == src ? 1.0 : 0.0;
+      for (int64_t r = 0; r < a.g.rows; ++r) a.own[r * kMsSources + s] = a.g.lo + r == src ? 1.0 : 0.0;
+    }
+    static void store_forward(const MsBcArgs& a, int64_t r, int s, Sum sum) {
+      a.own[r * kMsSources + s] = sum;
+      if (!(sum <= DBL_MAX)) *a.overflow |= 1ull << s;  // (out of double's range: the engine fails the batch)
+    }
+    // delta; own[r][s] turns from sigma into the coefficient
+    static double store_backward(const MsBcArgs& a, int64_t r, int s, Sum acc) {
+      const double sigma = a.own[r * kMsSources + s];
+      const double delta = sigma * acc;
+      a.own[r * kMsSources + s] = (1.0 + delta) / sigma;
+      return delta;
+    }
+  };
+  struct BcWide {
+    using Sum = WideSum;
+    static Sum sum_zero() { return wide_sum_zero(); }
+    static void add(Sum& sum, const MsBcArgs& a, int64_t w, int s) { wide_add(sum, wide_load(a.wval, w, s)); }
+    static void init(const MsBcArgs& a, int s, int64_t src) {
+      for (int64_t v = 0; v < a.m.lvl_rows; ++v) wide_store(a.wval, v, s, v == src ? wide_one() : wide_zero());
+      for (int64_t r = 0; r < a.g.rows; ++r) wide_store(a.wown, r, s, a.g.lo + r == src ? wide_one() : wide_zero());
+    }
+    static void store_forward(const MsBcArgs& a, int64_t r, int s, Sum sum) {
+      wide_store(a.wown, r, s, wide_normalise(sum));
+    }
+    static double store_backward(const MsBcArgs& a, int64_t r, int s, Sum acc) {
+      const Wide sigma = wide_load(a.wown, r, s);
+      const double delta = wide_delta(sigma, acc);
+      wide_store(a.wown, r, s, wide_coefficient(delta, sigma));
+      return delta;
+    }
+  };
+  template <class F>
+  static void bc_value_type(const MsBcArgs& a, F&& f) {
+    if (a.wide) {
+      DBFS_CHECK(a.wval && a.wown, "MsBcArgs: wide without wval / wown");
+      f(BcWide{});
+    } else {
+      f(BcF64{});
+    }
+  }
+  template <class V>
+  static typename V::Sum bc_row_sum(const MsBcArgs& a, int64_t r, int s, int want) {
+    typename V::Sum sum = V::sum_zero();
     if (want == ms_unreached(a.m.lvl_bytes)) return sum;
     for (eid_t e = a.row_off[r]; e < a.row_off[r + 1]; ++e) {
       const vid_t w = a.col[e];
-      if (level_at(a.m, w, s) == want) sum += a.val[static_cast<int64_t>(w) * kMsSources + s];
+      if (level_at(a.m, w, s) == want) V::add(sum, a, static_cast<int64_t>(w), s);
     }
     return sum;
   }
   void ms_bc_init(const MsBcArgs& a) override {
-    for (int s = 0; s < kMsSources; ++s) {
-      const int64_t src = s < a.m.k ? a.m.src[s] : -1;
-      for (int64_t v = 0; v < a.m.lvl_rows; ++v) a.val[v * kMsSources + s] = v == src ? 1.0 : 0.0;
-      for (int64_t r = 0; r < a.g.rows; ++r) a.own[r * kMsSources + s] = a.g.lo + r == src ? 1.0 : 0.0;
-    }
+    bc_value_type(a, [&](auto val) {
+      for (int s = 0; s < kMsSources; ++s) decltype(val)::init(a, s, s < a.m.k ? a.m.src[s] : -1);
+    });
   }
   // (the host loops walk every row themselves, the listed long ones included)
   void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
@@ -371,41 +418,42 @@ class CpuBackend final : public Backend {
     }
   }
   void ms_bc_forward(const MsBcArgs& a) override {
-    for (int64_t r = 0; r < a.g.rows; ++r) {
-      bool any = false;
-      for (int s = 0; s < a.m.k; ++s) {
-        if (level_at(a.m, a.g.lo + r, s) != a.level) continue;
-        any = true;
-        const double sum = bc_row_sum(a, r, s, a.level - 1);
-        a.own[r * kMsSources + s] = sum;
-        if (!(sum <= DBL_MAX)) *a.overflow |= 1ull << s;  // (out of double's range: the engine fails the batch)
+    bc_value_type(a, [&](auto val) {
+      using V = decltype(val);
+      for (int64_t r = 0; r < a.g.rows; ++r) {
+        bool any = false;
+        for (int s = 0; s < a.m.k; ++s) {
+          if (level_at(a.m, a.g.lo + r, s) != a.level) continue;
+          any = true;
+          V::store_forward(a, r, s, bc_row_sum<V>(a, r, s, a.level - 1));
+        }
+        if (any && a.walked) ++*a.walked;
       }
-      if (any && a.walked) ++*a.walked;
-    }
+    });
   }
   void ms_bc_backward(const MsBcArgs& a) override {
-    for (int64_t r = 0; r < a.g.rows; ++r) {
-      const int64_t v = a.g.lo + r;
-      double lane[kMsSources] = {};
-      bool any = false, counts = false;
-      for (int s = 0; s < a.m.k; ++s) {
-        if (level_at(a.m, v, s) != a.level) continue;
-        any = true;
-        const double acc = a.leaf ? 0.0 : bc_row_sum(a, r, s, a.level + 1);
-        const double sigma = a.own[r * kMsSources + s];
-        const double delta = sigma * acc;
-        a.own[r * kMsSources + s] = (1.0 + delta) / sigma;
-        if (v != a.m.src[s]) {
-          lane[s] = delta;
-          counts = true;
+    bc_value_type(a, [&](auto val) {
+      using V = decltype(val);
+      for (int64_t r = 0; r < a.g.rows; ++r) {
+        const int64_t v = a.g.lo + r;
+        double lane[kMsSources] = {};
+        bool any = false, counts = false;
+        for (int s = 0; s < a.m.k; ++s) {
+          if (level_at(a.m, v, s) != a.level) continue;
+          any = true;
+          const double delta = V::store_backward(a, r, s, a.leaf ? V::sum_zero() : bc_row_sum<V>(a, r, s, a.level + 1));
+          if (v != a.m.src[s]) {
+            lane[s] = delta;
+            counts = true;
+          }
         }
+        if (any && a.walked) ++*a.walked;
+        if (!counts) continue;
+        for (int off = kMsSources / 2; off > 0; off >>= 1)
+          for (int i = 0; i < off; ++i) lane[i] += lane[i + off];
+        a.dep[r] += lane[0];
       }
-      if (any && a.walked) ++*a.walked;
-      if (!counts) continue;
-      for (int off = kMsSources / 2; off > 0; off >>= 1)
-        for (int i = 0; i < off; ++i) lane[i] += lane[i + off];
-      a.dep[r] += lane[0];
-    }
+    });
   }
   void* alloc_mapped(size_t bytes, void** dptr) override {
     void* h = std::calloc(1, std::max<size_t>(bytes, 1));

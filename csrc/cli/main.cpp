@@ -62,6 +62,7 @@ struct Args {
   std::string batch_dir = "auto";
   bool betweenness = false;           // --batch --betweenness: path counts and dependencies after every pass
   std::string betweenness_out;        // ... the raw dependency sums, one %.17g per vertex
+  std::string betweenness_counts;     // ... the path counts' form: double | wide | auto (empty: not given, double)
   bool oracle = true;
   bool validate = false;
   std::string levels_out;
@@ -88,6 +89,8 @@ struct Args {
                "       --batch --validate (every pass's levels checked on the device, all its sources at once)\n"
                "       --batch --betweenness [--betweenness-out FILE] (betweenness centrality of the K roots on the device:\n"
                "                   the raw dependency sums, checked against the sequential oracle unless --no-oracle)\n"
+               "       --betweenness-counts double|wide|auto (path counts as doubles: more than 2^1024 paths is an error;\n"
+               "                   as a mantissa and an exponent; or wide only for the passes that overflow a double)\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only; --batch and --validate work on the in-edge shard,\n"
@@ -133,6 +136,7 @@ Args parse(int argc, char** argv) {
     else if (s == "--batch-direction") a.batch_dir = next();
     else if (s == "--betweenness") a.betweenness = true;
     else if (s == "--betweenness-out") a.betweenness_out = next();
+    else if (s == "--betweenness-counts") a.betweenness_counts = next();
     else if (s == "--no-oracle") a.oracle = false;
     else if (s == "--validate") a.validate = true;
     else if (s == "--levels-out") a.levels_out = next();
@@ -165,6 +169,11 @@ Args parse(int argc, char** argv) {
   if ((a.betweenness || !a.betweenness_out.empty()) && !(a.batch && a.roots > 0))
     usage("--betweenness needs --roots K --batch");
   if (!a.betweenness_out.empty() && !a.betweenness) usage("--betweenness-out needs --betweenness");
+  if (!a.betweenness_counts.empty()) {
+    if (!a.betweenness) usage("--betweenness-counts needs --betweenness");
+    if (a.betweenness_counts != "double" && a.betweenness_counts != "wide" && a.betweenness_counts != "auto")
+      usage("--betweenness-counts must be double, wide or auto");
+  }
   if (a.directed) {
     // a single-source traversal is top-down only (the bottom-up kernels take
     // their degrees from their own rows); --batch pulls over the in-edge shard
@@ -614,6 +623,8 @@ int main(int argc, char** argv) {
       bopt.keep_levels = a.oracle || a.validate || a.betweenness;
       bopt.validate = a.validate;
       bopt.betweenness = a.betweenness;
+      if (!a.betweenness_counts.empty()) bopt.counts = parse_batch_counts(a.betweenness_counts);
+      const bool wide_counts = bopt.counts != BatchCounts::Double;
       std::vector<BatchResult> bres(static_cast<size_t>(nlocal));
       std::vector<lvl_t> blv;
       std::vector<double> bdep;
@@ -664,6 +675,7 @@ int main(int argc, char** argv) {
             if (bdep[v] > bdep[top]) top = v;
           std::printf("batch betweenness sources %zu bc_ms %.3f max vertex %zu score %.17g\n", roots.size(), b.bc_ms, top,
                       bdep.empty() ? 0.0 : bdep[top]);
+          if (wide_counts) std::printf("batch betweenness wide passes %d of %d\n", b.wide_count_passes, b.passes);
           if (!a.betweenness_out.empty()) {
             std::FILE* f = std::fopen(a.betweenness_out.c_str(), "w");
             DBFS_CHECK(f != nullptr, "cannot write " + a.betweenness_out);
@@ -672,7 +684,8 @@ int main(int argc, char** argv) {
           }
           if (check) {
             // the sequential oracle: relative error 1e-9, an exact 0 where it has one
-            const std::vector<double> exp = cpu_betweenness(full, roots, a.directed).dep;
+            // (wide or auto counts: the oracle's wide form)
+            const std::vector<double> exp = cpu_betweenness(full, roots, a.directed, false, wide_counts).dep;
             for (size_t v = 0; v < exp.size(); ++v) {
               const double g = bdep[v], e = exp[v];
               const bool ok = std::isfinite(g) && (e == 0.0 ? g == 0.0 : std::fabs(g - e) <= 1e-9 * std::fabs(e));
@@ -691,6 +704,7 @@ int main(int argc, char** argv) {
             char ms[64];
             std::snprintf(ms, sizeof(ms), "%.6f", b.bc_ms);
             extra = std::string(",\"bc_ms\":") + ms;
+            if (wide_counts) extra += ",\"wide_count_passes\":" + std::to_string(b.wide_count_passes);
           }
           if (a.validate) {
             char ms[64];

@@ -12,6 +12,7 @@
 // that level's active list (MsPushArgs::clear_list).  No level clears a whole
 // array.
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cstring>
 #include <utility>
@@ -55,6 +56,23 @@ void copy_transposed(Backend& be, const TDev* dev, int64_t rows, int k, THost* h
   }
 }
 
+// The same for a wide value matrix (dbfs/wide.hpp: a 768-byte record per
+// vertex) into the host's mantissa and exponent rows.
+void copy_transposed_wide(Backend& be, const unsigned char* dev, int64_t rows, int k, double* mant, int32_t* exp,
+                          size_t stride) {
+  std::vector<unsigned char> h(static_cast<size_t>(std::min(rows, kMsCopyRows)) * kWideRecord);
+  for (int64_t r0 = 0; r0 < rows; r0 += kMsCopyRows) {
+    const int64_t nr = std::min(kMsCopyRows, rows - r0);
+    be.to_host(h.data(), dev + static_cast<size_t>(r0) * kWideRecord, static_cast<size_t>(nr) * kWideRecord);
+    for (int64_t r = 0; r < nr; ++r)
+      for (int t = 0; t < k; ++t) {
+        const Wide x = wide_load(h.data(), r, t);
+        mant[static_cast<size_t>(t) * stride + static_cast<size_t>(r0 + r)] = x.m;
+        exp[static_cast<size_t>(t) * stride + static_cast<size_t>(r0 + r)] = x.e;
+      }
+  }
+}
+
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -67,6 +85,13 @@ BatchDirection parse_batch_direction(const std::string& s) {
   if (s == "pull") return BatchDirection::Pull;
   if (s == "alternate") return BatchDirection::Alternate;
   throw Error("batch direction must be auto, push, pull or alternate: '" + s + "'");
+}
+
+BatchCounts parse_batch_counts(const std::string& s) {
+  if (s == "double") return BatchCounts::Double;
+  if (s == "wide") return BatchCounts::Wide;
+  if (s == "auto") return BatchCounts::Auto;
+  throw Error("batch counts must be double, wide or auto: '" + s + "'");
 }
 
 int Engine::run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out) {
@@ -289,7 +314,16 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, const BatchOp
   out.sources = sources;
   out.passes = static_cast<int>(div_up(k, kMsSources));
   kept_ = BatchKept{};
-  if (o.keep_path_counts) kept_.counts.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), 0.0);
+  kept_.counts_wide = o.counts != BatchCounts::Double;
+  if (o.keep_path_counts) {
+    const size_t cnt = static_cast<size_t>(k) * static_cast<size_t>(part_.n);
+    if (kept_.counts_wide) {
+      kept_.counts_mant.assign(cnt, 0.0);
+      kept_.counts_exp.assign(cnt, 0);
+    } else {
+      kept_.counts.assign(cnt, 0.0);
+    }
+  }
   if (o.keep_levels) kept_.levels.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.n), kUnreached);
   if (o.keep_parents) kept_.parents.assign(static_cast<size_t>(k) * static_cast<size_t>(part_.part), -1);
   if (o.validate) out.violations.assign(static_cast<size_t>(k) * kMsCheckCounters, 0);
@@ -350,7 +384,7 @@ BatchResult Engine::run_batch(const std::vector<int64_t>& sources, const BatchOp
       }
       int depth = 0;
       for (int t = 0; t < kp; ++t) depth = std::max(depth, out.depth[static_cast<size_t>(first + t)]);
-      bc_batch_pass(m, depth, o.betweenness, o.keep_path_counts, first, out);
+      bc_batch_pass(m, depth, o.betweenness, o.keep_path_counts, first, o.counts, out);
     }
   }
   out.ms = comm_.max_host(ms);
@@ -447,23 +481,19 @@ void Engine::check_batch_pass(const MsPassMatrix& m, int64_t* viol, bool parents
 // launch.  A directed graph's forward sweep walks the in-edge shard, the
 // backward one the out-edges.
 void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bool counts, int64_t first,
-                           BatchResult& out) {
+                           BatchCounts form, BatchResult& out) {
+  static_assert(kWideLanes == kMsSources, "a wide record holds one value per source");
   const auto t0 = std::chrono::steady_clock::now();
   const int P = part_.nranks;
   const int64_t W = part_.part, n = part_.n;
   MsBuffers& b = *ms_;
   const size_t own_vals = static_cast<size_t>(W) * kMsSources;
-  if (b.bc_val.size() == 0) {
-    b.bc_val = DBuf<double>(be_, own_vals * P);
-    if (P > 1) b.bc_own = DBuf<double>(be_, own_vals);
-    b.bc_walked = DBuf<unsigned long long>(be_, 2);  // (rows walked; MsBcArgs::overflow)
-  }
+  const size_t own_wide = static_cast<size_t>(W) * kWideRecord;
+  if (b.bc_walked.size() == 0) b.bc_walked = DBuf<unsigned long long>(be_, 2);  // (rows walked; MsBcArgs::overflow)
   be_.memset_async(b.bc_walked.data(), 0, b.bc_walked.bytes());
   MsBcArgs a;
   a.g = g_.view();
   a.m = m;
-  a.val = b.bc_val.data();
-  a.own = P > 1 ? b.bc_own.data() : b.bc_val.data();
   a.dep = accumulate ? b.bc_dep.data() : nullptr;
   a.walked = b.bc_walked.data();
   a.overflow = b.bc_walked.data() + 1;
@@ -492,34 +522,77 @@ void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bo
     a.n_long = b.bc_long_n[which];
   };
   auto share = [&] {  // (several ranks: every rank's new lines into every rank's matrix)
-    if (P > 1) comm_.allgather(b.bc_own.data(), b.bc_val.data(), own_vals * sizeof(double));
+    if (P == 1) return;
+    if (a.wide) comm_.allgather(b.bc_wown.data(), b.bc_wval.data(), own_wide);
+    else comm_.allgather(b.bc_own.data(), b.bc_val.data(), own_vals * sizeof(double));
   };
-  be_.ms_bc_init(a);
-  // forward: the predecessor rows
   const ShardView pred = check_view();
-  a.row_off = pred.row_off;
-  a.col = pred.col;
-  a.nnz = pred.nnz;
-  long_rows(0, pred);
-  for (int level = 1; level < depth; ++level) {
-    a.level = level;
-    be_.ms_bc_forward(a);
-    share();
-    ++out.bc_launches;
+  // (Auto: once in doubles, and once more, wide, when that forward sweep overflowed)
+  for (a.wide = form == BatchCounts::Wide;; a.wide = true) {
+    if (a.wide) {
+      if (b.bc_wval.size() == 0) {
+        b.bc_wval = DBuf<unsigned char>(be_, own_wide * P);
+        if (P > 1) b.bc_wown = DBuf<unsigned char>(be_, own_wide);
+      }
+      a.wval = b.bc_wval.data();
+      a.wown = P > 1 ? b.bc_wown.data() : b.bc_wval.data();
+    } else {
+      if (b.bc_val.size() == 0) {
+        b.bc_val = DBuf<double>(be_, own_vals * P);
+        if (P > 1) b.bc_own = DBuf<double>(be_, own_vals);
+      }
+      a.val = b.bc_val.data();
+      a.own = P > 1 ? b.bc_own.data() : b.bc_val.data();
+    }
+    be_.ms_bc_init(a);
+    // forward: the predecessor rows
+    a.row_off = pred.row_off;
+    a.col = pred.col;
+    a.nnz = pred.nnz;
+    long_rows(0, pred);
+    for (int level = 1; level < depth; ++level) {
+      a.level = level;
+      be_.ms_bc_forward(a);
+      share();
+      ++out.bc_launches;
+    }
+    if (a.wide) break;  // (no count leaves the wide range)
+    if (fault_.kind == "bc_device" && fault_.rank == comm_.rank()) be_.inject_device_check();
+    // A count past DBL_MAX is inf, and the backward sweep's inf * 0 would be
+    // NaN: the batch fails here, on every rank, before a count is copied out
+    // (Auto: the pass starts again in the wide form, on every rank).
+    unsigned long long over = 0;
+    be_.to_host(&over, a.overflow, sizeof(over));
+    if (P > 1)
+      for (int64_t x : comm_.allgather_host_i64(static_cast<int64_t>(over))) over |= static_cast<unsigned long long>(x);
+    if (over == 0ull) break;
+    if (form != BatchCounts::Auto)
+      throw Error("run_batch: the shortest-path counts from source " + std::to_string(m.src[__builtin_ctzll(over)]) +
+                  " exceed the range of a double; betweenness and path counts are not available for this graph");
   }
-  if (fault_.kind == "bc_device" && fault_.rank == comm_.rank()) be_.inject_device_check();
-  // A count past DBL_MAX is inf, and the backward sweep's inf * 0 would be
-  // NaN: the batch fails here, on every rank, before a count is copied out.
-  unsigned long long over = 0;
-  be_.to_host(&over, a.overflow, sizeof(over));
-  if (P > 1)
-    for (int64_t x : comm_.allgather_host_i64(static_cast<int64_t>(over))) over |= static_cast<unsigned long long>(x);
-  if (over != 0ull)
-    throw Error("run_batch: the shortest-path counts from source " + std::to_string(m.src[__builtin_ctzll(over)]) +
-                " exceed the range of a double; betweenness and path counts are not available for this graph");
-  if (counts)
-    copy_transposed(be_, b.bc_val.data(), n, m.k, kept_.counts.data() + static_cast<size_t>(first) * static_cast<size_t>(n),
-                    static_cast<size_t>(n), [](double x) { return x; });
+  if (a.wide) {
+    ++out.wide_count_passes;
+    if (form == BatchCounts::Wide && fault_.kind == "bc_device" && fault_.rank == comm_.rank())
+      be_.inject_device_check();
+  }
+  if (counts) {
+    const size_t at = static_cast<size_t>(first) * static_cast<size_t>(n);
+    if (a.wide) {
+      copy_transposed_wide(be_, b.bc_wval.data(), n, m.k, kept_.counts_mant.data() + at, kept_.counts_exp.data() + at,
+                           static_cast<size_t>(n));
+    } else if (kept_.counts_wide) {  // (Auto, a pass that stayed in doubles: frexp on the host)
+      copy_transposed(be_, b.bc_val.data(), n, m.k, kept_.counts_mant.data() + at, static_cast<size_t>(n),
+                      [](double x) { return x; });
+      for (size_t i = at; i < at + static_cast<size_t>(m.k) * static_cast<size_t>(n); ++i) {
+        const Wide x = wide_from_double(kept_.counts_mant[i]);
+        kept_.counts_mant[i] = x.m;
+        kept_.counts_exp[i] = x.e;
+      }
+    } else {
+      copy_transposed(be_, b.bc_val.data(), n, m.k, kept_.counts.data() + at, static_cast<size_t>(n),
+                      [](double x) { return x; });
+    }
+  }
   be_.synchronize();
   const auto t1 = std::chrono::steady_clock::now();
   if (accumulate) {
@@ -568,7 +641,31 @@ std::vector<double> Engine::gather_betweenness() {
 
 std::vector<double> Engine::gather_batch_path_counts() {
   DBFS_CHECK(kept_.counts_k > 0, "gather_batch_path_counts: no batch has run with keep_path_counts");
-  return kept_.counts;
+  if (!kept_.counts_wide) return kept_.counts;
+  std::vector<double> out(kept_.counts_mant.size());
+  for (size_t i = 0; i < out.size(); ++i) {
+    out[i] = wide_to_double(Wide{kept_.counts_mant[i], kept_.counts_exp[i]});
+    DBFS_CHECK(out[i] <= DBL_MAX,
+               "gather_batch_path_counts: a shortest-path count exceeds the range of a double; "
+               "gather_batch_path_counts_wide / batch_path_counts_wide return mantissas and exponents");
+  }
+  return out;
+}
+
+void Engine::gather_batch_path_counts_wide(std::vector<double>& mant, std::vector<int32_t>& exp) {
+  DBFS_CHECK(kept_.counts_k > 0, "gather_batch_path_counts_wide: no batch has run with keep_path_counts");
+  if (kept_.counts_wide) {
+    mant = kept_.counts_mant;
+    exp = kept_.counts_exp;
+    return;
+  }
+  mant.resize(kept_.counts.size());
+  exp.resize(kept_.counts.size());
+  for (size_t i = 0; i < mant.size(); ++i) {
+    const Wide x = wide_from_double(kept_.counts[i]);
+    mant[i] = x.m;
+    exp[i] = x.e;
+  }
 }
 
 std::vector<int64_t> Engine::validate_batch_pass(const std::vector<int64_t>& sources) {

@@ -77,15 +77,52 @@ CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src) {
   return r;
 }
 
-CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t>& sources, bool directed,
-                                     bool want_counts) {
-  DBFS_CHECK(g.row_lo == 0 && g.rows == g.n, "cpu_betweenness expects a full CSR");
+namespace {
+
+// cpu_betweenness' two count forms: a count, how it is added, tested, kept,
+// and the ratio sigma[v] / sigma[w] of the backward pass (a double: at most 1).
+struct OracleF64 {
+  using T = double;
+  static T zero() { return 0.0; }
+  static T one() { return 1.0; }
+  static void add(T& sum, T x) { sum += x; }
+  static T finish(T sum) { return sum; }
+  static bool in_range(T x) { return x <= DBL_MAX; }
+  static double ratio(T v, T w) { return v / w; }
+  static void keep(CpuBetweennessResult& r, const std::vector<T>& sigma, size_t at) {
+    std::copy(sigma.begin(), sigma.end(), r.sigma.begin() + at);
+  }
+  static void reserve(CpuBetweennessResult& r, size_t cnt) { r.sigma.assign(cnt, 0.0); }
+};
+struct OracleWide {
+  using T = Wide;  // (running sums between add and finish, the stored form otherwise)
+  static T zero() { return wide_zero(); }
+  static T one() { return wide_one(); }
+  // (a sum that holds nothing is (0, 0) here, not wide_sum_zero(): wide_add takes a zero from either side)
+  static void add(T& sum, T x) { wide_add(sum, x); }
+  static T finish(T sum) { return wide_normalise(sum); }
+  static bool in_range(T) { return true; }
+  static double ratio(T v, T w) { return wide_div_to_double(v, w); }
+  static void keep(CpuBetweennessResult& r, const std::vector<T>& sigma, size_t at) {
+    for (size_t v = 0; v < sigma.size(); ++v) r.sigma_mant[at + v] = sigma[v].m, r.sigma_exp[at + v] = sigma[v].e;
+  }
+  static void reserve(CpuBetweennessResult& r, size_t cnt) {
+    r.sigma_mant.assign(cnt, 0.0);
+    r.sigma_exp.assign(cnt, 0);
+  }
+};
+
+template <class V>
+CpuBetweennessResult cpu_betweenness_as(const HostCSR& g, const std::vector<int64_t>& sources, bool directed,
+                                        bool want_counts) {
+  using T = typename V::T;
   const size_t n = static_cast<size_t>(g.n);
   CpuBetweennessResult r;
   r.dep.assign(n, 0.0);
-  if (want_counts) r.sigma.assign(sources.size() * n, 0.0);
+  if (want_counts) V::reserve(r, sources.size() * n);
   std::vector<lvl_t> dist(n);
-  std::vector<double> sigma(n), delta(n);
+  std::vector<T> sigma(n);
+  std::vector<double> delta(n);
   std::vector<vid_t> order;  // the queue; read backwards it is Brandes' stack
   order.reserve(n);
   // (a count past DBL_MAX is inf, and the dependencies above it NaN: as Engine::run_batch, an error)
@@ -97,22 +134,22 @@ CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t
     const int64_t src = sources[i];
     DBFS_CHECK(src >= 0 && src < g.n, "source vertex out of range");
     std::fill(dist.begin(), dist.end(), kUnreached);
-    std::fill(sigma.begin(), sigma.end(), 0.0);
+    std::fill(sigma.begin(), sigma.end(), V::zero());
     std::fill(delta.begin(), delta.end(), 0.0);
     order.clear();
     order.push_back(static_cast<vid_t>(src));
     dist[src] = 0;
-    sigma[src] = 1.0;
+    sigma[src] = V::one();
     for (size_t head = 0; head < order.size(); ++head) {
       const vid_t u = order[head];
       const lvl_t lu = dist[u];
       if (!directed && lu > 0) {
         // u's predecessors are in its own row, all dequeued before it
-        double s = 0.0;
+        T s = V::zero();
         for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e)
-          if (dist[g.col[e]] == lu - 1) s += sigma[g.col[e]];
-        sigma[u] = s;
-        DBFS_CHECK(s <= DBL_MAX, over(src));
+          if (dist[g.col[e]] == lu - 1) V::add(s, sigma[g.col[e]]);
+        sigma[u] = V::finish(s);
+        DBFS_CHECK(V::in_range(sigma[u]), over(src));
       }
       for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e) {
         const vid_t w = g.col[e];
@@ -122,8 +159,9 @@ CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t
         }
         // (u's count is final: every vertex one level closer was dequeued before it)
         if (directed && dist[w] == lu + 1) {
-          sigma[w] += sigma[u];
-          DBFS_CHECK(sigma[w] <= DBL_MAX, over(src));
+          V::add(sigma[w], sigma[u]);
+          sigma[w] = V::finish(sigma[w]);
+          DBFS_CHECK(V::in_range(sigma[w]), over(src));
         }
       }
     }
@@ -132,14 +170,23 @@ CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t
       double d = 0.0;
       for (eid_t e = g.row_off[v]; e < g.row_off[v + 1]; ++e) {
         const vid_t w = g.col[e];
-        if (dist[w] == dist[v] + 1) d += sigma[v] / sigma[w] * (1.0 + delta[w]);
+        if (dist[w] == dist[v] + 1) d += V::ratio(sigma[v], sigma[w]) * (1.0 + delta[w]);
       }
       delta[v] = d;
       if (static_cast<int64_t>(v) != src) r.dep[v] += d;
     }
-    if (want_counts) std::copy(sigma.begin(), sigma.end(), r.sigma.begin() + i * n);
+    if (want_counts) V::keep(r, sigma, i * n);
   }
   return r;
+}
+
+}  // namespace
+
+CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t>& sources, bool directed,
+                                     bool want_counts, bool wide) {
+  DBFS_CHECK(g.row_lo == 0 && g.rows == g.n, "cpu_betweenness expects a full CSR");
+  return wide ? cpu_betweenness_as<OracleWide>(g, sources, directed, want_counts)
+              : cpu_betweenness_as<OracleF64>(g, sources, directed, want_counts);
 }
 
 int64_t traversed_edges(const HostCSR& g, const std::vector<lvl_t>& level) {

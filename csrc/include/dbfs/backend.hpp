@@ -23,6 +23,7 @@
 
 #include "dbfs/common.hpp"
 #include "dbfs/rmat.hpp"
+#include "dbfs/wide.hpp"
 
 namespace dbfs {
 
@@ -1253,6 +1254,18 @@ struct MsBcArgs {
   const vid_t* long_rows = nullptr;
   int64_t n_long = 0;
   int64_t split_above = 0;
+  // Extended-range form (dbfs/wide.hpp): every value is a mantissa and an
+  // exponent, wval / wown take the places of val / own (which are not read),
+  // one 768-byte record per vertex -- its kMsSources mantissas, then their
+  // exponents -- and the same rules hold with wide sums: forward stores the
+  // normalised count and sets no overflow bit; backward keeps sigma, acc and
+  // the coefficient wide and leaves delta = sigma * acc, at most n, as a
+  // double (0 when below 2^-1074); the lanes' tree and dep are as above.
+  // Each rounding is the double form's: where every count and coefficient is
+  // a normal double, both forms give the same bits.
+  bool wide = false;
+  unsigned char* wval = nullptr;    // m.lvl_rows records
+  unsigned char* wown = nullptr;    // g.rows records
 };
 
 // ---- backend ----------------------------------------------------------------

@@ -460,12 +460,21 @@ struct RunResult {
 enum class BatchDirection { Auto, Push, Pull, Alternate };
 BatchDirection parse_batch_direction(const std::string& s);
 
+// The number format of a batch's shortest-path counts (betweenness /
+// keep_path_counts).  Double: doubles, a count past DBL_MAX fails the batch.
+// Wide: dbfs/wide.hpp's mantissa and exponent in every pass, no range error.
+// Auto: a pass runs in doubles and, if its forward sweep overflowed, its
+// sweeps are redone wide.
+enum class BatchCounts { Double, Wide, Auto };
+BatchCounts parse_batch_counts(const std::string& s);
+
 // What a batch does besides the traversal (Engine::run_batch describes each).
 struct BatchOptions {
   BatchDirection direction = BatchDirection::Auto;
   bool keep_levels = true;
   bool validate = false, keep_parents = false;
   bool betweenness = false, keep_path_counts = false;
+  BatchCounts counts = BatchCounts::Double;
 };
 
 // One level of one pass: form 'P' push, 'L' pull; the active vertices it
@@ -512,6 +521,10 @@ struct BatchResult {
   // the launch's level: launches x owned rows without that skip).
   double bc_ms = 0.0, bc_forward_ms = 0.0, bc_backward_ms = 0.0;
   int64_t bc_launches = 0, bc_rows_walked = 0;
+  // the passes whose counts ran in the wide form (BatchCounts::Wide: all;
+  // Auto: those redone -- their double sweeps' time, launches and rows are in
+  // the figures above too)
+  int wide_count_passes = 0;
 };
 
 // Fault injection for failure-detection tests (see Engine::inject_fault).
@@ -565,7 +578,14 @@ class Engine {
   // Path counts are doubles: a batch in which a source has more than DBL_MAX
   // (~2^1024) shortest paths to some vertex throws after that pass's forward
   // sweep, on every rank, naming the first such source, and leaves no result
-  // (extended-range counts: not implemented).
+  // -- BatchOptions::counts = Double, the default.  Wide runs every pass with
+  // extended-range counts and coefficients (a mantissa and an exponent,
+  // MsBcArgs::wide: 768 + 8 bytes per owned vertex, allocated on first use)
+  // and never fails for range; Auto runs a pass in doubles and redoes its
+  // sweeps wide when the overflow mask, agreed across the ranks, is set.
+  // BatchResult::wide_count_passes.  The dependency sums are doubles in every
+  // form: a source's share below 2^-1074 counts as 0.  Kept path counts are
+  // held as mantissa and exponent whenever counts is not Double.
   BatchResult run_batch(const std::vector<int64_t>& sources, const BatchOptions& o = {});
   // The last batch's dependency sums, one per vertex: dep(v) = the sum over the
   // source slots i with v != src_i of delta_{src_i}(v) -- raw: not halved on
@@ -575,7 +595,12 @@ class Engine {
   // The last batch's shortest-path counts, [k][n] row-major (0 where source k
   // does not reach; exact while below 2^53).  Throws when the batch ran
   // without keep_path_counts.
+  // After a Wide or Auto batch: the same doubles when every count fits one,
+  // an error naming gather_batch_path_counts_wide otherwise.
   std::vector<double> gather_batch_path_counts();
+  // The same counts as mant * 2^exp, [k][n] each, in frexp's convention (mant
+  // in [0.5, 1); (0.0, 0) for 0), after a batch of any counts form.
+  void gather_batch_path_counts_wide(std::vector<double>& mant, std::vector<int32_t>& exp);
   int64_t batch_path_count_sources() const { return kept_.counts_k; }  // (-1: none)
   // The last batch's levels, [k][n] row-major, kUnreached where source k does
   // not reach; collective.  Throws when the batch ran without keep_levels.
@@ -735,6 +760,9 @@ class Engine {
     // sums of the owned rows, the rows-walked counter followed by the overflow
     // mask (MsBcArgs::walked, ::overflow)
     DBuf<double> bc_val, bc_own, bc_dep;
+    // the wide form's value matrix and owned records (MsBcArgs::wval, ::wown),
+    // allocated by the first pass that runs wide
+    DBuf<unsigned char> bc_wval, bc_wown;
     DBuf<unsigned long long> bc_walked;
     // MsBcArgs::long_rows of the predecessor rows [0] and the out-rows [1]
     // (an undirected graph: [0] for both), built on first use for
@@ -760,7 +788,11 @@ class Engine {
     // owned slices of the parent trees, [k][part] (-1: unreached or padding)
     std::vector<int64_t> parents;
     int64_t parents_k = -1;      // sources of the last batch with parents (-1: none)
-    std::vector<double> counts;  // path counts, [k][n]
+    std::vector<double> counts;  // path counts, [k][n] (BatchCounts::Double) ...
+    // ... or as mantissa and exponent (Wide, Auto)
+    std::vector<double> counts_mant;
+    std::vector<int32_t> counts_exp;
+    bool counts_wide = false;
     int64_t counts_k = -1;       // sources of the last batch with path counts (-1: none)
     bool dep_valid = false;      // the last batch accumulated dependencies
   };
@@ -775,8 +807,11 @@ class Engine {
   // Path counts and dependencies of the pass m (the deepest of its sources
   // `depth` levels): dependencies into MsBuffers::bc_dep (accumulate), path
   // counts into rows [first, first + k) of kept_.counts (counts).  Blocking;
-  // the forward and backward times are added to `out`.
-  void bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bool counts, int64_t first, BatchResult& out);
+  // the forward and backward times are added to `out`.  form: Double throws
+  // on an overflowed count, Wide runs the wide kernels, Auto redoes the pass
+  // wide (init, forward, backward) instead of throwing.
+  void bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bool counts, int64_t first, BatchCounts form,
+                     BatchResult& out);
   // reference-mode state
   bool ref_ready_ = false;
   DBuf<lvl_t> dist_;

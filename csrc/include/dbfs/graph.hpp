@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dbfs/common.hpp"
+#include "dbfs/wide.hpp"
 
 namespace dbfs {
 
@@ -102,12 +103,19 @@ CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src);
 // from their tails' rows); otherwise g is symmetric and v's own row lists them.
 // sigma (want_counts): [k][n] row-major, 0 where unreached.  Throws, naming
 // the source, when a count exceeds DBL_MAX (as Engine::run_batch does).
+// wide: the counts are kept as dbfs/wide.hpp's mantissa and exponent, added
+// in the same order, and nothing throws for range; sigma[v] / sigma[w] leaves
+// the wide form as a double (0 when below 2^-1074), dep is doubles as before,
+// and the counts (want_counts) come as sigma_mant * 2^sigma_exp in frexp's
+// convention ((0.0, 0) where unreached) instead of sigma.
 struct CpuBetweennessResult {
   std::vector<double> dep;
   std::vector<double> sigma;
+  std::vector<double> sigma_mant;
+  std::vector<int32_t> sigma_exp;
 };
 CpuBetweennessResult cpu_betweenness(const HostCSR& g, const std::vector<int64_t>& sources, bool directed,
-                                     bool want_counts = false);
+                                     bool want_counts = false, bool wide = false);
 
 // Traversed undirected edges (Graph500 convention): sum of degrees over
 // reached vertices / 2.

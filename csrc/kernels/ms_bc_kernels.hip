@@ -18,8 +18,16 @@
 // floating-point values, the same bits on every run.  A forward count past
 // DBL_MAX sets its source's bit in MsBcArgs::overflow (an integer OR) and the
 // engine fails the batch before the backward sweep.
+//
+// Every kernel is templated on the value type next to the level type: MsBcF64
+// (doubles, the 512-B line above) or MsBcWide (dbfs/wide.hpp: a mantissa and
+// an exponent, a 768-B record per vertex -- 64 mantissas, then 64 exponents, so
+// a lane's two loads hit adjacent lines).  The wide form has no overflow mask,
+// its coefficients stay wide (they underflow a double exactly when counts
+// overflow it), and delta = sigma * acc leaves it as a double.
 #include <cfloat>
 
+#include "dbfs/wide.hpp"
 #include "ms_walk.hpp"
 
 namespace dbfs {
@@ -39,34 +47,96 @@ __device__ __forceinline__ double wave_sum_f64(double x) {
   return x;
 }
 
+// The value types.  T: a stored value; Sum: a lane's running sum; val / own:
+// MsBcArgs' matrices; load / store: lane's value of row v; finish: a forward
+// sum as it is stored, in_range: whether it may be; turn: delta = sigma * acc
+// and sigma's coefficient (1 + delta) / sigma; LDS: what the long rows' 16
+// partial sums meet in.
+struct MsBcF64 {
+  using T = double;
+  using Sum = double;
+  using Mat = double;
+  static __device__ __forceinline__ const Mat* val(const MsBcArgs& a) { return a.val; }
+  static __device__ __forceinline__ Mat* own(const MsBcArgs& a) { return a.own; }
+  static __device__ __forceinline__ T zero() { return 0.0; }
+  static __device__ __forceinline__ T one() { return 1.0; }
+  static __device__ __forceinline__ Sum sum_zero() { return 0.0; }
+  static __device__ __forceinline__ T load(const Mat* m, int64_t v, int lane) { return m[v * kMsSources + lane]; }
+  static __device__ __forceinline__ void store(Mat* m, int64_t v, int lane, T x) { m[v * kMsSources + lane] = x; }
+  // (stored row order; + 0.0 changes no bit of a sum >= 0)
+  static __device__ __forceinline__ void add(Sum& sum, T x) { sum += x; }
+  static __device__ __forceinline__ T finish(Sum sum) { return sum; }
+  static __device__ __forceinline__ bool in_range(Sum sum) { return sum <= DBL_MAX; }
+  static __device__ __forceinline__ double turn(T sigma, Sum acc, T& coef) {
+    const double delta = sigma * acc;
+    coef = (1.0 + delta) / sigma;
+    return delta;
+  }
+  struct LDS {
+    double part[1024 / kWave][kWave];
+    __device__ __forceinline__ void put(int w, int lane, Sum x) { part[w][lane] = x; }
+    __device__ __forceinline__ Sum get(int w, int lane) const { return part[w][lane]; }
+  };
+};
+struct MsBcWide {
+  using T = Wide;
+  using Sum = WideSum;
+  using Mat = unsigned char;
+  static __device__ __forceinline__ const Mat* val(const MsBcArgs& a) { return a.wval; }
+  static __device__ __forceinline__ Mat* own(const MsBcArgs& a) { return a.wown; }
+  static __device__ __forceinline__ T zero() { return wide_zero(); }
+  static __device__ __forceinline__ T one() { return wide_one(); }
+  static __device__ __forceinline__ Sum sum_zero() { return wide_sum_zero(); }
+  static __device__ __forceinline__ T load(const Mat* m, int64_t v, int lane) { return wide_load(m, v, lane); }
+  static __device__ __forceinline__ void store(Mat* m, int64_t v, int lane, T x) { wide_store(m, v, lane, x); }
+  static __device__ __forceinline__ void add(Sum& sum, T x) { wide_add(sum, x); }
+  static __device__ __forceinline__ T finish(Sum sum) { return wide_normalise(sum); }
+  static __device__ __forceinline__ bool in_range(Sum) { return true; }  // (no overflow mask in this form)
+  // (sigma, acc and the coefficient wide; delta, at most n, a double: 0 when below 2^-1074)
+  static __device__ __forceinline__ double turn(T sigma, Sum acc, T& coef) {
+    const double delta = wide_delta(sigma, acc);
+    coef = wide_coefficient(delta, sigma);
+    return delta;
+  }
+  struct LDS {
+    double m[1024 / kWave][kWave];
+    int32_t e[1024 / kWave][kWave];
+    __device__ __forceinline__ void put(int w, int lane, Sum x) { m[w][lane] = x.m, e[w][lane] = x.e; }
+    __device__ __forceinline__ Sum get(int w, int lane) const { return Sum{m[w][lane], e[w][lane]}; }
+  };
+};
+
+template <class V>
 __global__ __launch_bounds__(kMsBcBlock) void ms_bc_init_kernel(MsBcArgs a) {
   const int lane = lane_id();
   const int64_t my_src = ((a.m.batch_mask >> lane) & 1ull) ? a.m.src[lane] : -1;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * (kMsBcBlock / kWave);
   const int64_t first = static_cast<int64_t>(blockIdx.x) * (kMsBcBlock / kWave) + (threadIdx.x >> 6);
-  for (int64_t v = first; v < a.m.lvl_rows; v += stride) a.val[v * kMsSources + lane] = v == my_src ? 1.0 : 0.0;
-  for (int64_t r = first; r < a.g.rows; r += stride) a.own[r * kMsSources + lane] = a.g.lo + r == my_src ? 1.0 : 0.0;
+  typename V::Mat* const val = const_cast<typename V::Mat*>(V::val(a));
+  for (int64_t v = first; v < a.m.lvl_rows; v += stride) V::store(val, v, lane, v == my_src ? V::one() : V::zero());
+  for (int64_t r = first; r < a.g.rows; r += stride)
+    V::store(V::own(a), r, lane, a.g.lo + r == my_src ? V::one() : V::zero());
 }
 
 // The sum, per lane, of val[w][lane] over the entries w of row [rs, re) whose
 // level is `want` -- for the lanes with `at` set; the others load no value.
-template <class L>
-__device__ __forceinline__ double ms_bc_row_sum(const MsBcArgs& a, const L* __restrict__ lvl, eid_t rs, eid_t re,
-                                                bool at, int want) {
+template <class L, class V>
+__device__ __forceinline__ typename V::Sum ms_bc_row_sum(const MsBcArgs& a, const L* __restrict__ lvl, eid_t rs,
+                                                         eid_t re, bool at, int want) {
   constexpr int kNone = ms_unreached<L>();
-  const double* __restrict__ val = a.val;
+  const typename V::Mat* __restrict__ val = V::val(a);
   const int lane = lane_id();
-  double sum = 0.0;
+  typename V::Sum sum = V::sum_zero();
   ms_walk_row<L, kMsWalkAhead>(lvl, a.col, rs, re, a.m.lvl_rows, 28, [&](int valid, const vid_t* w, const int* lw) {
-    double x[kMsWalkAhead];  // (the group's value loads: issued together, after its level lines)
+    typename V::T x[kMsWalkAhead];  // (the group's value loads: issued together, after its level lines)
 #pragma unroll
     for (int i = 0; i < kMsWalkAhead; ++i) {
       // (&, not &&: a branch on the wave-uniform i < valid would take the entry's level load along)
       const bool take = (i < valid) & at & (lw[i] == want) & (lw[i] != kNone);
-      x[i] = take ? val[static_cast<int64_t>(w[i]) * kMsSources + lane] : 0.0;
+      x[i] = take ? V::load(val, static_cast<int64_t>(w[i]), lane) : V::zero();
     }
 #pragma unroll
-    for (int i = 0; i < kMsWalkAhead; ++i) sum += x[i];  // (stored row order; + 0.0 changes no bit of a sum >= 0)
+    for (int i = 0; i < kMsWalkAhead; ++i) V::add(sum, x[i]);  // (stored row order)
     return true;
   });
   return sum;
@@ -77,28 +147,33 @@ __device__ __forceinline__ double ms_bc_row_sum(const MsBcArgs& a, const L* __re
 // (the engine fails the batch on it).  The caller ORs them in a scalar and
 // stores once, after its rows: an atomic inside the row loop would turn the
 // loop's scalar row-offset loads into vector loads.  Wave-uniform call.
-__device__ __forceinline__ unsigned long long ms_bc_store_forward(const MsBcArgs& a, int64_t r, bool at, double sum) {
-  if (at) a.own[r * kMsSources + lane_id()] = sum;
-  return __ballot(at && !(sum <= DBL_MAX));
+// The wide form stores the normalised sum and has no such lanes.
+template <class V>
+__device__ __forceinline__ unsigned long long ms_bc_store_forward(const MsBcArgs& a, int64_t r, bool at,
+                                                                  typename V::Sum sum) {
+  if (at) V::store(V::own(a), r, lane_id(), V::finish(sum));
+  return __ballot(at && !V::in_range(sum));
 }
 
 // A vertex's backward result from acc, the sum of its successors'
 // coefficients: delta, the vertex's own coefficient in place of sigma, and
 // its share of dep.  Wave-uniform call.
-__device__ __forceinline__ void ms_bc_store_backward(const MsBcArgs& a, int64_t r, bool at, bool counts, double acc) {
+template <class V>
+__device__ __forceinline__ void ms_bc_store_backward(const MsBcArgs& a, int64_t r, bool at, bool counts,
+                                                     typename V::Sum acc) {
   const int lane = lane_id();
   double delta = 0.0;
   if (at) {  // (reached: sigma >= 1; no other lane divides)
-    const double sigma = a.own[r * kMsSources + lane];
-    delta = sigma * acc;
-    a.own[r * kMsSources + lane] = (1.0 + delta) / sigma;
+    typename V::T coef;
+    delta = V::turn(V::load(V::own(a), r, lane), acc, coef);
+    V::store(V::own(a), r, lane, coef);
   }
   if (__ballot(counts) == 0ull) return;
   const double mine = wave_sum_f64(counts ? delta : 0.0);
   if (lane == 0) a.dep[r] += mine;  // (one wave per vertex and launch: a plain store)
 }
 
-template <class L>
+template <class L, class V>
 __global__ __launch_bounds__(kMsBcBlock) void ms_bc_forward_kernel(MsBcArgs a) {
   const ShardView& g = a.g;
   const L* __restrict__ lvl = static_cast<const L*>(a.m.lvl);
@@ -116,13 +191,13 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_forward_kernel(MsBcArgs a) {
     DBFS_DCHECK(rs >= 0 && rs <= re && re <= a.nnz, 29, r);
     if (a.n_long > 0 && re - rs > a.split_above) continue;  // (ms_bc_long_kernel's)
     ++walked;
-    over |= ms_bc_store_forward(a, r, at, ms_bc_row_sum<L>(a, lvl, rs, re, at, a.level - 1));
+    over |= ms_bc_store_forward<V>(a, r, at, ms_bc_row_sum<L, V>(a, lvl, rs, re, at, a.level - 1));
   }
   if (a.walked && lane == 0 && walked) atomicAdd(a.walked, walked);
-  if (lane == 0 && over) atomicOr(a.overflow, over);
+  if (lane == 0 && over) atomicOr(a.overflow, over);  // (wide: never)
 }
 
-template <class L>
+template <class L, class V>
 __global__ __launch_bounds__(kMsBcBlock) void ms_bc_backward_kernel(MsBcArgs a) {
   const ShardView& g = a.g;
   const L* __restrict__ lvl = static_cast<const L*>(a.m.lvl);
@@ -137,15 +212,15 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_backward_kernel(MsBcArgs a) 
     DBFS_DCHECK(v < a.m.lvl_rows, 27, v);
     const bool at = on && static_cast<int>(lvl[v * kMsSources + lane]) == a.level;
     if (__ballot(at) == 0ull) continue;
-    double acc = 0.0;
+    typename V::Sum acc = V::sum_zero();
     if (!a.leaf) {
       const eid_t rs = a.row_off[r], re = a.row_off[r + 1];
       DBFS_DCHECK(rs >= 0 && rs <= re && re <= a.nnz, 29, r);
       if (a.n_long > 0 && re - rs > a.split_above) continue;  // (ms_bc_long_kernel's)
-      acc = ms_bc_row_sum<L>(a, lvl, rs, re, at, a.level + 1);
+      acc = ms_bc_row_sum<L, V>(a, lvl, rs, re, at, a.level + 1);
     }
     ++walked;
-    ms_bc_store_backward(a, r, at, at && v != my_src, acc);
+    ms_bc_store_backward<V>(a, r, at, at && v != my_src, acc);
   }
   if (a.walked && lane == 0 && walked) atomicAdd(a.walked, walked);
 }
@@ -158,9 +233,10 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_backward_kernel(MsBcArgs a) 
 constexpr int kMsBcLongBlock = 1024;
 constexpr int kMsBcLongWaves = kMsBcLongBlock / kWave;
 
-template <class L, bool kBackward>
+template <class L, class V, bool kBackward>
 __global__ __launch_bounds__(kMsBcLongBlock) void ms_bc_long_kernel(MsBcArgs a) {
-  __shared__ double s_part[kMsBcLongWaves][kWave];
+  static_assert(kMsBcLongWaves == 1024 / kWave, "MsBcF64::LDS, MsBcWide::LDS");
+  __shared__ typename V::LDS s_part;
   const ShardView& g = a.g;
   const L* __restrict__ lvl = static_cast<const L*>(a.m.lvl);
   const int lane = lane_id();
@@ -179,15 +255,15 @@ __global__ __launch_bounds__(kMsBcLongBlock) void ms_bc_long_kernel(MsBcArgs a) 
     DBFS_DCHECK(rs >= 0 && rs <= re && re <= a.nnz, 29, r);
     const eid_t chunk = (((re - rs + kMsBcLongWaves - 1) / kMsBcLongWaves) + kWave - 1) & ~static_cast<eid_t>(kWave - 1);
     const eid_t b = min(re, rs + wave * chunk), en = min(re, b + chunk);
-    s_part[wave][lane] = ms_bc_row_sum<L>(a, lvl, b, en, at, kBackward ? a.level + 1 : a.level - 1);
+    s_part.put(wave, lane, ms_bc_row_sum<L, V>(a, lvl, b, en, at, kBackward ? a.level + 1 : a.level - 1));
     __syncthreads();
     if (wave == 0) {
-      double sum = 0.0;
+      typename V::Sum sum = V::sum_zero();
 #pragma unroll
-      for (int w = 0; w < kMsBcLongWaves; ++w) sum += s_part[w][lane];
+      for (int w = 0; w < kMsBcLongWaves; ++w) V::add(sum, s_part.get(w, lane));
       ++walked;
-      if (kBackward) ms_bc_store_backward(a, r, at, at && v != my_src, sum);
-      else over |= ms_bc_store_forward(a, r, at, sum);
+      if (kBackward) ms_bc_store_backward<V>(a, r, at, at && v != my_src, sum);
+      else over |= ms_bc_store_forward<V>(a, r, at, sum);
     }
     __syncthreads();  // (s_part is the next row's)
   }
@@ -206,17 +282,31 @@ __global__ __launch_bounds__(kMsBcBlock) void ms_bc_long_rows_kernel(const eid_t
   }
 }
 
+// f(V{}) with the value type MsBcArgs::wide selects.
+template <class F>
+void ms_bc_value_type(const MsBcArgs& a, F&& f) {
+  if (a.wide) {
+    DBFS_CHECK(a.wval && a.wown, "MsBcArgs: wide without wval / wown");
+    f(MsBcWide{});
+  } else {
+    f(MsBcF64{});
+  }
+}
+
 // One level of a sweep: the rows by their wave, then the long ones.
 template <bool kBackward>
 void ms_bc_sweep(const MsBcArgs& a, hipStream_t st) {
   if (a.g.rows <= 0) return;
   const unsigned grid = grid_for(a.g.rows, kMsBcBlock / kWave, kMsBcGrid);
-  ms_level_type(a.m.lvl_bytes, [&](auto l) {
-    using L = decltype(l);
-    if (kBackward) ms_bc_backward_kernel<L><<<grid, kMsBcBlock, 0, st>>>(a);
-    else ms_bc_forward_kernel<L><<<grid, kMsBcBlock, 0, st>>>(a);
-    if (a.n_long > 0)
-      ms_bc_long_kernel<L, kBackward><<<grid_for(a.n_long, 1, kMsBcGrid), kMsBcLongBlock, 0, st>>>(a);
+  ms_bc_value_type(a, [&](auto val) {
+    using V = decltype(val);
+    ms_level_type(a.m.lvl_bytes, [&](auto l) {
+      using L = decltype(l);
+      if (kBackward) ms_bc_backward_kernel<L, V><<<grid, kMsBcBlock, 0, st>>>(a);
+      else ms_bc_forward_kernel<L, V><<<grid, kMsBcBlock, 0, st>>>(a);
+      if (a.n_long > 0)
+        ms_bc_long_kernel<L, V, kBackward><<<grid_for(a.n_long, 1, kMsBcGrid), kMsBcLongBlock, 0, st>>>(a);
+    });
   });
 }
 
@@ -224,11 +314,13 @@ void ms_bc_sweep(const MsBcArgs& a, hipStream_t st) {
 
 void ms_bc_init(const MsBcArgs& a, hipStream_t st) {
   if (a.m.lvl_rows <= 0) return;
-  ms_bc_init_kernel<<<grid_for(a.m.lvl_rows, kMsBcBlock / kWave, kMsBcGrid), kMsBcBlock, 0, st>>>(a);
+  ms_bc_value_type(a, [&](auto val) {
+    ms_bc_init_kernel<decltype(val)><<<grid_for(a.m.lvl_rows, kMsBcBlock / kWave, kMsBcGrid), kMsBcBlock, 0, st>>>(a);
+  });
 }
 
 void ms_bc_forward(const MsBcArgs& a, hipStream_t st) {
-  DBFS_CHECK(a.overflow, "ms_bc_forward: MsBcArgs::overflow missing");
+  DBFS_CHECK(a.overflow || a.wide, "ms_bc_forward: MsBcArgs::overflow missing");
   ms_bc_sweep<false>(a, st);
 }
 void ms_bc_backward(const MsBcArgs& a, hipStream_t st) { ms_bc_sweep<true>(a, st); }

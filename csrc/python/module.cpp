@@ -194,21 +194,31 @@ PYBIND11_MODULE(_dbfs_native, m) {
   m.def("write_levels", [](const std::string& path, py::array_t<int32_t, py::array::c_style | py::array::forcecast> l) {
     write_levels(path, from_numpy<int32_t>(l));
   });
-  // sequential Brandes oracle: (dep float64 [n], path counts float64 [k, n] or None)
+  // sequential Brandes oracle: (dep float64 [n], path counts float64 [k, n] or None);
+  // wide_counts: extended-range counts, the second value is (mant float64 [k, n], exp int32 [k, n])
   m.def(
       "cpu_betweenness",
-      [](const HostCSR& g, const std::vector<int64_t>& sources, bool directed, bool path_counts) -> py::tuple {
+      [](const HostCSR& g, const std::vector<int64_t>& sources, bool directed, bool path_counts,
+         bool wide_counts) -> py::tuple {
         CpuBetweennessResult r;
         {
           py::gil_scoped_release rel;
-          r = cpu_betweenness(g, sources, directed, path_counts);
+          r = cpu_betweenness(g, sources, directed, path_counts, wide_counts);
         }
         if (!path_counts) return py::make_tuple(to_numpy(r.dep), py::none());
+        if (wide_counts) {
+          py::array_t<double> mant = to_numpy(r.sigma_mant);
+          py::array_t<int32_t> exp = to_numpy(r.sigma_exp);
+          mant.resize({static_cast<py::ssize_t>(sources.size()), static_cast<py::ssize_t>(g.n)});
+          exp.resize({static_cast<py::ssize_t>(sources.size()), static_cast<py::ssize_t>(g.n)});
+          return py::make_tuple(to_numpy(r.dep), py::make_tuple(mant, exp));
+        }
         py::array_t<double> sg = to_numpy(r.sigma);
         sg.resize({static_cast<py::ssize_t>(sources.size()), static_cast<py::ssize_t>(g.n)});
         return py::make_tuple(to_numpy(r.dep), sg);
       },
-      py::arg("csr"), py::arg("sources"), py::arg("directed") = false, py::arg("path_counts") = false);
+      py::arg("csr"), py::arg("sources"), py::arg("directed") = false, py::arg("path_counts") = false,
+      py::arg("wide_counts") = false);
   m.def(
       "cpu_bfs",
       [](const HostCSR& g, int64_t src) {
@@ -727,6 +737,7 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def_readonly("bc_backward_ms", &BatchResult::bc_backward_ms)
       .def_readonly("bc_launches", &BatchResult::bc_launches)
       .def_readonly("bc_rows_walked", &BatchResult::bc_rows_walked)
+      .def_readonly("wide_count_passes", &BatchResult::wide_count_passes)
       // run_batch(validate=True): per source (gap, cross, orphan); else empty
       .def_property_readonly("violations",
                              [](const BatchResult& r) {
@@ -793,8 +804,9 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def(
           "run_batch",
           [](Engine& e, const std::vector<int64_t>& sources, const std::string& direction, bool levels, bool validate,
-             bool parents, bool betweenness, bool path_counts) {
+             bool parents, bool betweenness, bool path_counts, const std::string& counts) {
             BatchOptions o;
+            o.counts = parse_batch_counts(counts);
             o.direction = parse_batch_direction(direction);
             o.keep_levels = levels;
             o.validate = validate;
@@ -809,7 +821,8 @@ PYBIND11_MODULE(_dbfs_native, m) {
             return r;
           },
           py::arg("sources"), py::arg("direction") = "auto", py::arg("levels") = true, py::arg("validate") = false,
-          py::arg("parents") = false, py::arg("betweenness") = false, py::arg("path_counts") = false)
+          py::arg("parents") = false, py::arg("betweenness") = false, py::arg("path_counts") = false,
+          py::arg("counts") = "double")
       // the last batch's raw dependency sums: float64 [n]
       .def("gather_betweenness",
            [](Engine& e) {
@@ -833,6 +846,23 @@ PYBIND11_MODULE(_dbfs_native, m) {
              py::array_t<double> a = to_numpy(v);
              a.resize({static_cast<py::ssize_t>(k), static_cast<py::ssize_t>(k ? v.size() / k : 0)});
              return a;
+           })
+      // the same as (mant float64 [k, n], exp int32 [k, n]), count = mant * 2^exp
+      .def("gather_batch_path_counts_wide",
+           [](Engine& e) {
+             std::vector<double> mv;
+             std::vector<int32_t> ev;
+             int64_t k = 0;
+             {
+               py::gil_scoped_release rel;
+               e.gather_batch_path_counts_wide(mv, ev);
+               k = e.batch_path_count_sources();
+             }
+             py::array_t<double> mant = to_numpy(mv);
+             py::array_t<int32_t> exp = to_numpy(ev);
+             mant.resize({static_cast<py::ssize_t>(k), static_cast<py::ssize_t>(k ? mv.size() / k : 0)});
+             exp.resize({static_cast<py::ssize_t>(k), static_cast<py::ssize_t>(k ? ev.size() / k : 0)});
+             return py::make_tuple(mant, exp);
            })
       .def("build_in_edges", &Engine::build_in_edges, py::call_guard<py::gil_scoped_release>())
       .def("gather_batch_parents",

@@ -91,11 +91,13 @@ class BatchResult:
     (never part of ``ms`` or ``check_ms``), its ``bc_forward_ms`` /
     ``bc_backward_ms`` parts, ``bc_launches`` (one per level and direction)
     and ``bc_rows_walked`` (the rows those launches walked on this rank: the
-    ones with a source on the launch's level); zeros without them."""
+    ones with a source on the launch's level); zeros without them.
+    ``wide_count_passes``: the passes whose counts ran in the extended-range
+    form (``run_batch(wide_counts=True)``: all; ``"auto"``: those redone)."""
 
     __slots__ = ("sources", "ms", "gteps", "passes", "wide_levels", "reached", "edges", "depth", "dist_sum",
                  "discovered", "levels", "violations", "validated", "check_ms", "bc_ms", "bc_forward_ms",
-                 "bc_backward_ms", "bc_launches", "bc_rows_walked")
+                 "bc_backward_ms", "bc_launches", "bc_rows_walked", "wide_count_passes")
 
     def __init__(self, r: Any, validate: bool = False):
         self.violations = [tuple(int(x) for x in v) for v in r.violations] if validate else None
@@ -103,6 +105,7 @@ class BatchResult:
         self.check_ms = float(r.check_ms)
         self.bc_ms, self.bc_forward_ms, self.bc_backward_ms = float(r.bc_ms), float(r.bc_forward_ms), float(r.bc_backward_ms)
         self.bc_launches, self.bc_rows_walked = int(r.bc_launches), int(r.bc_rows_walked)
+        self.wide_count_passes = int(r.wide_count_passes)
         self.sources, self.ms, self.gteps, self.passes = list(r.sources), r.ms, r.gteps, r.passes
         self.wide_levels = bool(r.wide_levels)
         self.reached, self.edges, self.depth = list(r.reached), list(r.edges), list(r.depth)
@@ -211,7 +214,8 @@ class BFS:
         return [BFSResult.from_native(r) for r in self.engine.run_many([int(s) for s in sources])]
 
     def run_batch(self, sources, direction: str = "auto", levels: bool = True, validate: bool = False,
-                  parents: bool = False, betweenness: bool = False, path_counts: bool = False) -> BatchResult:
+                  parents: bool = False, betweenness: bool = False, path_counts: bool = False,
+                  wide_counts=False) -> BatchResult:
         """One concurrent traversal from all ``sources`` (64 per pass, one bit
         per source in a 64-bit word per vertex); collective like run().
         ``direction``: "auto" picks push or pull per level (one rank; several
@@ -240,7 +244,23 @@ class BFS:
         device.  Several ranks use a simple replicated form: correct, not fast.
         The counts are doubles: when a source has more than 2**1024 shortest
         paths to some vertex the call raises (on every rank, naming the source)
-        and leaves no result; it never returns a non-finite value."""
+        and leaves no result; it never returns a non-finite value.
+
+        ``wide_counts=True`` keeps counts and coefficients as a mantissa and
+        an exponent instead (768 + 8 bytes per owned vertex): no count is out
+        of range, nothing raises for it, and every rounding is the one the
+        doubles would make -- where all counts fit a double the results are
+        the same bits.  ``wide_counts="auto"`` runs each pass in doubles and
+        redoes only a pass that overflowed in the wide form:
+        ``BatchResult.wide_count_passes``.  batch_betweenness() stays float64
+        and finite (a single source's share below 2**-1074 counts as 0);
+        the counts are read with batch_path_counts_wide()."""
+        if isinstance(wide_counts, (bool, np.bool_)):
+            counts = "wide" if wide_counts else "double"
+        elif isinstance(wide_counts, str) and wide_counts == "auto":
+            counts = "auto"
+        else:
+            raise ValueError('wide_counts must be False, True or "auto"')
         if direction not in BATCH_DIRECTIONS:
             raise ValueError(f"direction must be one of {BATCH_DIRECTIONS}")
         if (validate or parents) and not levels:
@@ -248,7 +268,7 @@ class BFS:
         if (betweenness or path_counts) and not levels:
             raise ValueError("betweenness and path_counts read the level matrix (keep_levels): levels=True")
         return BatchResult(self.engine.run_batch([int(s) for s in sources], direction, bool(levels), bool(validate),
-                                                 bool(parents), bool(betweenness), bool(path_counts)),
+                                                 bool(parents), bool(betweenness), bool(path_counts), counts),
                            validate=bool(validate))
 
     def batch_betweenness(self) -> np.ndarray:
@@ -266,8 +286,18 @@ class BFS:
         float64 [k, n]: row i holds the number of shortest paths from
         sources[i] to every vertex (1 for the source itself, 0 where it does
         not reach), exact while below 2**53, rounded above (run_batch raises
-        where one would pass 2**1024).  k x n x 8 bytes on the host."""
+        where one would pass 2**1024).  k x n x 8 bytes on the host.  After a
+        batch with ``wide_counts``: the same doubles when every count fits
+        one; otherwise it raises, naming batch_path_counts_wide -- never a
+        non-finite value."""
         return self.engine.gather_batch_path_counts()
+
+    def batch_path_counts_wide(self):
+        """The same counts as ``(mant float64 [k, n], exp int32 [k, n])`` with
+        count == mant * 2.0**exp, in frexp's convention: mant in [0.5, 1), and
+        (0.0, 0) for a zero count.  After any run_batch(path_counts=True),
+        whatever its ``wide_counts``."""
+        return self.engine.gather_batch_path_counts_wide()
 
     def batch_levels(self) -> np.ndarray:
         """Levels of the last run_batch as int32 [k, n] (UNREACHED where a

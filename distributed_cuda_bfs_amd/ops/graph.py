@@ -81,14 +81,17 @@ def cpu_bfs(csr, src: int):
     return N.cpu_bfs(csr, int(src))
 
 
-def cpu_betweenness(csr, sources, directed: bool = False, path_counts: bool = False):
+def cpu_betweenness(csr, sources, directed: bool = False, path_counts: bool = False, wide_counts: bool = False):
     """Sequential Brandes oracle over the stored adjacency entries (duplicates
     are parallel edges, self-loops never lie on a shortest path): returns
     ``(dep float64 [n], sigma float64 [k, n] or None)`` with dep[v] the raw sum
     over the source slots i with v != sources[i] of source i's dependency on
     v -- the definition of ``BFS.batch_betweenness``.  ``directed``: the CSR
-    holds out-edges only (build_csr(directed=True))."""
-    return N.cpu_betweenness(csr, [int(s) for s in sources], bool(directed), bool(path_counts))
+    holds out-edges only (build_csr(directed=True)).  The counts are doubles
+    and a count past 2**1024 raises; ``wide_counts=True`` keeps them as a
+    mantissa and an exponent (same order of additions, nothing raises for
+    range) and returns sigma as ``(mant float64 [k, n], exp int32 [k, n])``."""
+    return N.cpu_betweenness(csr, [int(s) for s in sources], bool(directed), bool(path_counts), bool(wide_counts))
 
 
 def write_binary_csr(path: str, csr) -> None:
