@@ -23,9 +23,9 @@ LDLIBS    := -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -Wl,-rpath,
 
 HOST_SRC  := csrc/graph/io.cpp csrc/graph/csr.cpp csrc/backend/cpu_backend.cpp \
              csrc/backend/hip_backend.cpp csrc/comm/comm.cpp csrc/comm/nccl_comm.cpp \
-             csrc/comm/tcp_bootstrap.cpp csrc/comm/peer_comm.cpp csrc/comm/replay_comm.cpp csrc/engine/engine.cpp csrc/engine/batch.cpp csrc/engine/device_loop.cpp csrc/graph/shard_reader.cpp
+             csrc/comm/tcp_bootstrap.cpp csrc/comm/peer_comm.cpp csrc/comm/replay_comm.cpp csrc/engine/engine.cpp csrc/engine/batch.cpp csrc/engine/device_loop.cpp csrc/engine/components.cpp csrc/graph/shard_reader.cpp
 HIP_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/graph_kernels.hip csrc/kernels/ref_kernels.hip \
-             csrc/kernels/graph_sort.hip csrc/kernels/peer_kernels.hip csrc/kernels/ms_kernels.hip csrc/kernels/ms_bc_kernels.hip
+             csrc/kernels/graph_sort.hip csrc/kernels/peer_kernels.hip csrc/kernels/ms_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip
 
 HOST_OBJ  := $(patsubst csrc/%.cpp,$(BUILD)/%.o,$(HOST_SRC))
 HIP_OBJ   := $(patsubst csrc/%.hip,$(BUILD)/%.o,$(HIP_SRC))
@@ -44,7 +44,7 @@ lib: $(CORE_LIB)
 # verified on the device; the first violation fails the run on the host,
 # HipBackend::take_device_check).  Host code and the other kernels unchanged.
 CHECKED_BUILD := build-checked
-CHECKED_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/ms_bc_kernels.hip
+CHECKED_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip
 CHECKED_OBJ   := $(patsubst csrc/%.hip,$(CHECKED_BUILD)/%.o,$(CHECKED_SRC))
 checked: bin/bfs_checked
 $(CHECKED_BUILD)/%.o: csrc/%.hip $(HEADERS)

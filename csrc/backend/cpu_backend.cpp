@@ -417,6 +417,56 @@ class CpuBackend final : public Backend {
       ++*count;
     }
   }
+  // connected components (CcArgs): the device's hook, one entry at a time
+  static void cc_hook(vid_t* comp, vid_t u, vid_t w) {
+    vid_t p1 = comp[u], p2 = comp[w];
+    while (p1 != p2) {
+      const vid_t hi = std::max(p1, p2), lo = std::min(p1, p2);
+      if (comp[hi] == hi) {
+        comp[hi] = lo;
+        break;
+      }
+      p1 = comp[hi];
+      p2 = comp[lo];
+    }
+  }
+  void cc_init(const CcArgs& a) override {
+    for (int64_t v = 0; v < a.g.n; ++v) a.comp[v] = static_cast<vid_t>(v);
+  }
+  void cc_link(const CcArgs& a) override {
+    for (int64_t r = 0; r < a.g.rows; ++r) {
+      const vid_t u = static_cast<vid_t>(a.g.lo + r);
+      const eid_t rs = std::min<eid_t>(a.g.row_off[r + 1], a.g.row_off[r] + a.first);
+      const eid_t re = a.count < 0 ? a.g.row_off[r + 1] : std::min<eid_t>(a.g.row_off[r + 1], rs + a.count);
+      if (a.skip && a.comp[u] == a.skip_label) continue;
+      for (eid_t e = rs; e < re; ++e) cc_hook(a.comp, u, a.g.col[e]);
+    }
+  }
+  void cc_link_pairs(const CcArgs& a) override {
+    for (int64_t i = 0; i < a.pairs; ++i) cc_hook(a.comp, static_cast<vid_t>(a.pair_lo + i), a.other[i]);
+  }
+  void cc_compress(const CcArgs& a) override {
+    // (ascending: comp[v] <= v, so v's parent already holds its root)
+    for (int64_t v = 0; v < a.g.n; ++v) a.comp[v] = a.comp[a.comp[v]];
+  }
+  void cc_sample(const CcArgs& a) override {
+    for (int i = 0; i < a.samples; ++i) a.sample_out[i] = a.comp[a.sample_idx[i]];
+  }
+  void cc_sizes(const CcArgs& a) override {
+    int64_t roots = 0, single = 0, best = 0, best_label = 0;
+    for (int64_t v = 0; v < a.g.n; ++v) a.size[v] = 0;
+    for (int64_t v = 0; v < a.g.n; ++v) ++a.size[a.comp[v]];
+    for (int64_t v = 0; v < a.g.n; ++v) {
+      if (a.comp[v] != static_cast<vid_t>(v)) continue;
+      ++roots;
+      single += a.size[v] == 1u ? 1 : 0;
+      if (static_cast<int64_t>(a.size[v]) > best) best = a.size[v], best_label = v;  // (ascending: ties keep the smaller)
+    }
+    a.totals[0] = roots;
+    a.totals[1] = single;
+    a.totals[2] = best;
+    a.totals[3] = best_label;
+  }
   void ms_bc_forward(const MsBcArgs& a) override {
     bc_value_type(a, [&](auto val) {
       using V = decltype(val);

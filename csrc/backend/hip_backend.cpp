@@ -254,6 +254,12 @@ class HipBackend final : public Backend {
   void td_sparse(const TdSparseArgs& a) override { on(); kern::td_sparse(a, st_); chk(); }
   void td_sparse_apply(const TdSparseArgs& a) override { on(); kern::td_sparse_apply(a, st_); chk(); }
   void level_finish(const LevelFinishArgs& a) override { on(); kern::level_finish(a, st_); chk(); }
+  void cc_init(const CcArgs& a) override { on(); kern::cc_init(a, st_); chk(); }
+  void cc_link(const CcArgs& a) override { on(); kern::cc_link(a, st_); chk(); }
+  void cc_link_pairs(const CcArgs& a) override { on(); kern::cc_link_pairs(a, st_); chk(); }
+  void cc_compress(const CcArgs& a) override { on(); kern::cc_compress(a, st_); chk(); }
+  void cc_sample(const CcArgs& a) override { on(); kern::cc_sample(a, st_); chk(); }
+  void cc_sizes(const CcArgs& a) override { on(); kern::cc_sizes(a, st_); chk(); }
   void widen_levels(const uint8_t* in, lvl_t* out, int64_t n, uint8_t base) override {
     on();
     kern::widen_levels(in, out, n, base, st_);

@@ -73,6 +73,9 @@ struct Args {
   bool phase_timing = false;
   bool hub_sort = true;
   bool directed = false;
+  bool components = false;            // --components: connected components before the traversals (Engine::components)
+  std::string components_out;         // ... the labels, one per line
+  int64_t cc_sample_entries = -1;     // --cc-sample-entries N (EngineOptions::cc_sample_entries; -1: the default)
   bool mode_given = false;            // --mode on the command line (--directed turns only the default into td)
 };
 
@@ -91,6 +94,9 @@ struct Args {
                "                   the raw dependency sums, checked against the sequential oracle unless --no-oracle)\n"
                "       --betweenness-counts double|wide|auto (path counts as doubles: more than 2^1024 paths is an error;\n"
                "                   as a mantissa and an exponent; or wide only for the passes that overflow a double)\n"
+               "       --components [--components-out FILE] (connected components on the device before the traversals: count,\n"
+               "                   largest, singletons; the labels checked against the sequential oracle unless --no-oracle)\n"
+               "       --cc-sample-entries N (entries per row hooked before the largest component is skipped; 0: one full pass)\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only; --batch and --validate work on the in-edge shard,\n"
@@ -137,6 +143,9 @@ Args parse(int argc, char** argv) {
     else if (s == "--betweenness") a.betweenness = true;
     else if (s == "--betweenness-out") a.betweenness_out = next();
     else if (s == "--betweenness-counts") a.betweenness_counts = next();
+    else if (s == "--components") a.components = true;
+    else if (s == "--components-out") a.components_out = next();
+    else if (s == "--cc-sample-entries") a.cc_sample_entries = std::stoll(next());
     else if (s == "--no-oracle") a.oracle = false;
     else if (s == "--validate") a.validate = true;
     else if (s == "--levels-out") a.levels_out = next();
@@ -174,6 +183,8 @@ Args parse(int argc, char** argv) {
     if (a.betweenness_counts != "double" && a.betweenness_counts != "wide" && a.betweenness_counts != "auto")
       usage("--betweenness-counts must be double, wide or auto");
   }
+  if (!a.components_out.empty() && !a.components) usage("--components-out needs --components");
+  if (a.cc_sample_entries < -1) usage("--cc-sample-entries must be >= 0");
   if (a.directed) {
     // a single-source traversal is top-down only (the bottom-up kernels take
     // their degrees from their own rows); --batch pulls over the in-edge shard
@@ -529,6 +540,7 @@ int main(int argc, char** argv) {
     eo.bu_lane_limit = a.bu_lane_limit;
     eo.phase_timing = a.phase_timing;
     eo.directed = a.directed;
+    if (a.cc_sample_entries >= 0) eo.cc_sample_entries = a.cc_sample_entries;
     run_ranks(ranks, [&](int i, RankCtx& rc) {
       const int rk = multiproc ? wrank : i;
       if (synth) rc.graph = DeviceGraph::generate(*rc.be, gp, part, rk);
@@ -557,6 +569,48 @@ int main(int argc, char** argv) {
         ingest_json += (r ? ",[" : "[") + std::to_string(b[r]) + "," + std::to_string(e[r]) + "," +
                        std::to_string(m[r]) + "]";
       ingest_json += "]";
+    }
+
+    // ---- connected components (--components), before the traversals ----
+    if (a.components) {
+      std::vector<ComponentsResult> cres(static_cast<size_t>(nlocal));
+      std::vector<int64_t> labels;
+      run_ranks(ranks, [&](int i, RankCtx& rc) {
+        cres[i] = rc.engine->components();
+        if (i == 0 && leader && ((a.oracle && have_host) || !a.components_out.empty()))
+          labels = rc.engine->gather_components();
+      }, vgroup.get());
+      if (leader) {
+        const ComponentsResult& c = cres[0];
+        std::printf("components %lld largest label %lld size %lld singletons %lld ms %.3f\n",
+                    static_cast<long long>(c.components), static_cast<long long>(c.largest_label),
+                    static_cast<long long>(c.largest_size), static_cast<long long>(c.singletons), c.ms);
+        if (a.oracle && have_host) {
+          const std::vector<int64_t> exp = cpu_components(full);
+          for (int64_t i = 0; i < n; ++i) {
+            if (labels[i] != exp[i]) {
+              std::printf("component %lld %lld %lld\n", static_cast<long long>(i), static_cast<long long>(labels[i]),
+                          static_cast<long long>(exp[i]));
+              std::printf("Wrong output!\n");
+              return 1;
+            }
+          }
+          if (!a.quiet) std::printf("Components OK!\n");
+        }
+        if (!a.components_out.empty()) {
+          std::FILE* f = std::fopen(a.components_out.c_str(), "w");
+          DBFS_CHECK(f != nullptr, "cannot write " + a.components_out);
+          for (int64_t l : labels) std::fprintf(f, "%lld\n", static_cast<long long>(l));
+          std::fclose(f);
+        }
+        if (a.json)
+          std::printf("{\"graph\":\"%s\",\"n\":%lld,\"ranks\":%d,\"components\":%lld,\"largest_label\":%lld,"
+                      "\"largest_size\":%lld,\"singletons\":%lld,\"ms\":%.6f,\"cc_link_ms\":%.6f,"
+                      "\"cc_compress_ms\":%.6f,\"cc_sampled\":%s}\n",
+                      gname.c_str(), static_cast<long long>(n), P, static_cast<long long>(c.components),
+                      static_cast<long long>(c.largest_label), static_cast<long long>(c.largest_size),
+                      static_cast<long long>(c.singletons), c.ms, c.link_ms, c.compress_ms, c.sampled ? "true" : "false");
+      }
     }
 
     // ---- the reference's single run from <src> ----

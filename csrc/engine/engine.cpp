@@ -87,6 +87,7 @@ void set_engine_option(EngineOptions& o, const std::string& name, double v) {
   else if (name == "list_cap_factor") o.list_cap_factor = v;
   else if (name == "direct_frontier") o.direct_frontier = v != 0;
   else if (name == "bc_split_row") o.bc_split_row = static_cast<int64_t>(v);
+  else if (name == "cc_sample_entries") o.cc_sample_entries = std::max<int64_t>(0, static_cast<int64_t>(v));
   else throw Error("unknown engine option '" + name + "'");
 }
 
@@ -128,7 +129,8 @@ std::vector<std::pair<std::string, double>> engine_option_map(const EngineOption
           {"bu_cut_ranks", static_cast<double>(o.bu_cut_ranks)},
           {"list_cap_factor", o.list_cap_factor},
           {"direct_frontier", o.direct_frontier ? 1.0 : 0.0},
-          {"bc_split_row", static_cast<double>(o.bc_split_row)}};
+          {"bc_split_row", static_cast<double>(o.bc_split_row)},
+          {"cc_sample_entries", static_cast<double>(o.cc_sample_entries)}};
 }
 
 // ---- DeviceGraph ----------------------------------------------------------------
@@ -687,7 +689,8 @@ void Engine::read_level_stats(int64_t* host_stats) {
 // a device-check violation (the run fails when it ends), `batch_device` the
 // same at level L of a batch pass (run_batch fails after the pass), `bc_device`
 // the same during a pass's dependency accumulation (run_batch(betweenness)
-// fails after it),
+// fails after it), `cc_device` the same during the link of components()
+// (which fails when it ends),
 // `in_edges_device` during DeviceGraph::build_in_edges, `delay` enqueues the
 // level ms late; kind=late_wg[,us=U] (every rank, every level) makes the
 // workgroups of a sparse top-down level that take no ticket start U us late
@@ -716,8 +719,8 @@ FaultSpec FaultSpec::from_env() {
   }
   DBFS_CHECK(f.kind == "throw" || f.kind == "exit" || f.kind == "hang" || f.kind == "device" || f.kind == "delay" ||
                  f.kind == "rccl_init" || f.kind == "peer_init" || f.kind == "late_wg" || f.kind == "batch_device" ||
-                 f.kind == "in_edges_device" || f.kind == "bc_device",
-             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|bc_device|in_edges_device|delay|rccl_init|"
+                 f.kind == "in_edges_device" || f.kind == "bc_device" || f.kind == "cc_device",
+             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|bc_device|cc_device|in_edges_device|delay|rccl_init|"
              "peer_init|late_wg");
   // (rccl_init / peer_init: the communicators' setup fails -- NcclComm /
   // PeerComm read them; late_wg: every sparse top-down level's ticket-less
@@ -748,7 +751,8 @@ void Engine::inject_batch_fault(int level) {
 }
 
 void Engine::inject_fault(int level) {
-  if (fault_.kind == "batch_device" || fault_.kind == "in_edges_device" || fault_.kind == "bc_device")
+  if (fault_.kind == "batch_device" || fault_.kind == "in_edges_device" || fault_.kind == "bc_device" ||
+      fault_.kind == "cc_device")
     return;  // (not a traversal's)
   if (fault_.rank != comm_.rank() || fault_.level != level) return;
   if (fault_.kind == "device") {

@@ -77,6 +77,34 @@ CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src) {
   return r;
 }
 
+// Sequential union-find (union by size, path halving), then every vertex
+// gets the smallest id of its set.  Shares nothing with the backends' hooks.
+std::vector<int64_t> cpu_components(const HostCSR& g) {
+  DBFS_CHECK(g.row_lo == 0 && g.rows == g.n, "cpu_components expects a full CSR");
+  const size_t n = static_cast<size_t>(g.n);
+  std::vector<int64_t> parent(n), weight(n, 1);
+  for (size_t v = 0; v < n; ++v) parent[v] = static_cast<int64_t>(v);
+  auto find = [&](int64_t x) {
+    while (parent[x] != x) {
+      parent[x] = parent[parent[x]];
+      x = parent[x];
+    }
+    return x;
+  };
+  for (int64_t u = 0; u < g.n; ++u)
+    for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e) {
+      int64_t a = find(u), b = find(g.col[e]);
+      if (a == b) continue;
+      if (weight[a] < weight[b]) std::swap(a, b);
+      parent[b] = a;
+      weight[a] += weight[b];
+    }
+  std::vector<int64_t> smallest(n, g.n), label(n);
+  for (int64_t v = g.n - 1; v >= 0; --v) smallest[find(v)] = v;  // (descending: the last write is the smallest)
+  for (int64_t v = 0; v < g.n; ++v) label[v] = smallest[find(v)];
+  return label;
+}
+
 namespace {
 
 // cpu_betweenness' two count forms: a count, how it is added, tested, kept,

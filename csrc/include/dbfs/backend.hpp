@@ -1268,6 +1268,56 @@ struct MsBcArgs {
   unsigned char* wown = nullptr;    // g.rows records
 };
 
+// Connected components (Engine::components): a hook-and-compress forest over
+// the adjacency shard.  comp has one entry per vertex of the whole graph
+// (g.n; several ranks: every rank its own replica); comp[v] <= v always, a
+// vertex with comp[v] == v is a root, and a tree's root is its smallest id.
+//   cc_init        comp[v] = v for every v < g.n.
+//   cc_link        for every owned row r and every stored entry w at positions
+//     [first, first + count) of the row (count < 0: to the row's end), hook
+//     (g.lo + r, w): while the two ends' trees have different roots, hang the
+//     larger root under the smaller id (a 32-bit compare-and-swap), else climb
+//     both trees.  Pointers only decrease, so the result after cc_compress
+//     does not depend on the order of the hooks.  With `skip`, a row whose
+//     comp[g.lo + r] == skip_label when the row is taken is not walked.
+//   cc_link_pairs  hook (pair_lo + i, other[i]) for i < pairs.
+//   cc_compress    comp[v] = the root of v's tree, for every v < g.n.
+//   cc_sample      sample_out[i] = comp[sample_idx[i]] for i < samples.
+//   cc_sizes       (compressed comp) size[l] = vertices with comp[v] == l, and
+//     totals[0..3] = roots, roots of size 1, the largest size, its label (the
+//     smaller label on a tie).
+// Self-loops and duplicate entries change nothing.  g.col holds plain vertex
+// ids; the hub-encoded copies are not read.
+constexpr int kCcTotals = 4;
+// HIP, cc_sizes: workgroups at most, each with a slot of kCcTotals partial totals.
+constexpr int kCcSizeGrid = 1024;
+struct CcArgs {
+  ShardView g;                     // the owned rows (lo, rows, row_off, col, nnz) and n
+  vid_t* comp = nullptr;           // g.n entries
+  // cc_link
+  int64_t first = 0, count = -1;
+  bool skip = false;
+  vid_t skip_label = 0;
+  // Long rows (HIP): rows with more than 1024 entries to walk are queued
+  // here by the first launch (long_count: one counter, zeroed by cc_link) and
+  // walked by the whole grid in a second one; long_cap >= g.nnz / 1024 + 1
+  // holds them all.
+  vid_t* long_rows = nullptr;
+  int64_t long_cap = 0;
+  unsigned long long* long_count = nullptr;
+  // cc_link_pairs
+  const vid_t* other = nullptr;
+  int64_t pair_lo = 0, pairs = 0;
+  // cc_sample
+  const vid_t* sample_idx = nullptr;
+  vid_t* sample_out = nullptr;
+  int samples = 0;
+  // cc_sizes
+  uint32_t* size = nullptr;        // g.n entries (zeroed by cc_sizes)
+  int64_t* totals = nullptr;       // kCcTotals
+  int64_t* slots = nullptr;        // HIP: kCcSizeGrid x kCcTotals
+};
+
 // ---- backend ----------------------------------------------------------------
 
 class Backend {
@@ -1490,6 +1540,13 @@ class Backend {
   // above, in some order (at most cap stored; *count zero on entry)
   virtual void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
                                unsigned long long* count) = 0;
+  // connected components (CcArgs)
+  virtual void cc_init(const CcArgs& a) = 0;
+  virtual void cc_link(const CcArgs& a) = 0;
+  virtual void cc_link_pairs(const CcArgs& a) = 0;
+  virtual void cc_compress(const CcArgs& a) = 0;
+  virtual void cc_sample(const CcArgs& a) = 0;
+  virtual void cc_sizes(const CcArgs& a) = 0;
 
  protected:
   std::function<void(double)> wait_watch_;

@@ -395,6 +395,13 @@ struct EngineOptions {
   // entries are walked by a workgroup of 16 waves in a launch of their own
   // (MsBcArgs::long_rows) instead of by one wave; 0: never.
   int64_t bc_split_row = 512;
+  // components(): one rank, undirected -- hook only the first
+  // cc_sample_entries entries of every row, take the most frequent label of a
+  // vertex sample, and skip that component's rows in the pass over the
+  // remaining entries (Afforest's subgraph sampling; the rows are degree-
+  // sorted, so the first entries are the hubs).  0: one pass over every entry,
+  // which directed graphs and several ranks always run.
+  int64_t cc_sample_entries = 2;
 };
 
 // Named access to the numeric tuning options (alpha, beta, bu_lane_limit,
@@ -527,6 +534,22 @@ struct BatchResult {
   int wide_count_passes = 0;
 };
 
+// Engine::components.  sample_entries < 0: EngineOptions::cc_sample_entries.
+struct ComponentsOptions {
+  int64_t sample_entries = -1;
+};
+
+struct ComponentsResult {
+  int64_t components = 0;      // connected components (weakly connected, on a directed graph)
+  int64_t largest_label = -1;  // the largest one's label (its smallest vertex; the smaller label on a tie)
+  int64_t largest_size = 0;
+  int64_t singletons = 0;      // components of one vertex
+  double ms = 0.0;             // wall time, max over ranks: link_ms + compress_ms + the sizes
+  double link_ms = 0.0;        // the hook launches (several ranks: the label exchange too)
+  double compress_ms = 0.0;    // the pointer-jumping launches
+  bool sampled = false;        // the sample-and-skip form ran
+};
+
 // Fault injection for failure-detection tests (see Engine::inject_fault).
 struct FaultSpec {
   int rank = -1, level = -1;
@@ -618,6 +641,27 @@ class Engine {
   // from the last pass of the last batch, against `sources` (as many as that
   // pass had, at most 64): [k][3] as BatchResult::violations; collective.
   std::vector<int64_t> validate_batch_pass(const std::vector<int64_t>& sources);
+  // Connected components of the whole graph on the device; collective.
+  // label[v] = the smallest vertex id of v's component; a directed graph: the
+  // weakly connected components (an entry u -> v joins u and v).  A hook-and-
+  // compress forest over the owned rows (Backend::cc_*): one pass over the
+  // entries and a pointer-jumping compress, not a traversal per component.
+  // One rank, undirected, sample_entries > 0: the sample-and-skip form
+  // (EngineOptions::cc_sample_entries).  Several ranks, the simple form: every
+  // rank links its rows into its own full-length label array, the arrays are
+  // all-gathered (in pieces) and each rank hooks every peer's (v, label[v])
+  // pairs into its own -- every rank ends with the same array.  The labels do
+  // not depend on the form, the rank count or the run.  Device state: 4 B per
+  // vertex of the whole graph for the labels and 4 B for the sizes, allocated
+  // by the first call and kept; apart from run / run_batch / validate state.
+  ComponentsResult components(const ComponentsOptions& o = {});
+  // The last components() call's labels, and every vertex's component size,
+  // for all n vertices (this rank's replica: no communication).  Throw when
+  // components() has not run.
+  std::vector<int64_t> gather_components();
+  std::vector<int64_t> gather_component_sizes();
+  bool has_components() const { return cc_ && cc_->valid; }
+  const ComponentsResult& last_components() const;
   // Test hook: overwrite source slot `slot`'s level of global `vertex` in the
   // resident level matrix (on its owner; level < 0: unreached), so a test can
   // plant a violation for validate_batch_pass to find.
@@ -772,6 +816,19 @@ class Engine {
     int64_t bc_long_above = 0;
   };
   std::unique_ptr<MsBuffers> ms_;
+  // connected-components state (csrc/engine/components.cpp), allocated by the
+  // first components() call; separate from everything above
+  struct CcBuffers {
+    DBuf<vid_t> comp;        // CcArgs::comp: n entries (several ranks: this rank's replica)
+    DBuf<uint32_t> size;     // CcArgs::size
+    DBuf<vid_t> long_rows;   // CcArgs::long_rows, with the counter
+    DBuf<unsigned long long> long_count;
+    DBuf<int64_t> totals, slots;
+    DBuf<vid_t> sample_idx, sample_out;
+    bool valid = false;      // comp and size hold the last call's result
+    ComponentsResult last;
+  };
+  std::unique_ptr<CcBuffers> cc_;
   // 0: done; 1: deeper than the level type holds (rerun wider)
   int run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out);
   void collect_batch_levels();

@@ -91,6 +91,12 @@ struct CpuBfsResult {
 };
 CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src);
 
+// Sequential connected-components oracle: label[v] = the smallest vertex id
+// in v's component, every stored entry u -> w joining u and w (a directed
+// CSR: the weakly connected components).  Self-loops and duplicates change
+// nothing; a vertex without entries is its own component.
+std::vector<int64_t> cpu_components(const HostCSR& g);
+
 // Sequential betweenness oracle (Brandes 2001: a queue, the visit order as a
 // stack, a predecessor scan), one source at a time.  Entries are the stored
 // adjacency entries, duplicates and self-loops kept: sigma_s(s) = 1, and for a

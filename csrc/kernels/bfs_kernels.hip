@@ -776,8 +776,8 @@ bool checks_enabled() {
 
 unsigned long long take_check_error() {
   // (each kernel file records into its own g_check; all are read and cleared)
-  const unsigned long long h[6] = {take_check_local(), take_check_td(), take_check_bu(), take_check_ms(),
-                                   take_check_ms_bc(), take_check_graph()};
+  const unsigned long long h[7] = {take_check_local(), take_check_td(), take_check_bu(), take_check_ms(),
+                                   take_check_ms_bc(), take_check_cc(), take_check_graph()};
   for (unsigned long long x : h)
     if (x) return x;
   return 0;

@@ -23,6 +23,7 @@ unsigned long long take_check_td();
 unsigned long long take_check_bu();
 unsigned long long take_check_ms();
 unsigned long long take_check_ms_bc();
+unsigned long long take_check_cc();
 unsigned long long take_check_graph();
 // A level's totals and finish from unscanned unit statistics, one workgroup
 // (bfs_kernels.hip; bottom-up levels without the fused finish).

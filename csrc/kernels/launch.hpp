@@ -75,6 +75,14 @@ void ms_bc_backward(const MsBcArgs& a, hipStream_t st);
 void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* list, int64_t cap,
                      unsigned long long* count, hipStream_t st);
 
+// cc_kernels.hip (connected components: CcArgs)
+void cc_init(const CcArgs& a, hipStream_t st);
+void cc_link(const CcArgs& a, hipStream_t st);
+void cc_link_pairs(const CcArgs& a, hipStream_t st);
+void cc_compress(const CcArgs& a, hipStream_t st);
+void cc_sample(const CcArgs& a, hipStream_t st);
+void cc_sizes(const CcArgs& a, hipStream_t st);
+
 // peer_kernels.hip (PeerComm: collectives through peer-mapped windows)
 constexpr int kMaxPeers = 16;
 struct PeerPushArgs {

@@ -230,6 +230,18 @@ PYBIND11_MODULE(_dbfs_native, m) {
         return py::make_tuple(to_numpy(r.level), to_numpy(r.parent_edge));
       },
       py::arg("csr"), py::arg("src"));
+  // sequential connected-components oracle: int64 [n], the smallest id of every vertex's component
+  m.def(
+      "cpu_components",
+      [](const HostCSR& g) {
+        std::vector<int64_t> r;
+        {
+          py::gil_scoped_release rel;
+          r = cpu_components(g);
+        }
+        return to_numpy(r);
+      },
+      py::arg("csr"));
 
   py::class_<GenParams>(m, "GenParams")
       .def_readonly("n", &GenParams::n)
@@ -759,6 +771,16 @@ PYBIND11_MODULE(_dbfs_native, m) {
                ", ms=" + std::to_string(r.ms) + ", gteps=" + std::to_string(r.gteps) + ")";
       });
 
+  py::class_<ComponentsResult>(m, "ComponentsResult")
+      .def_readonly("components", &ComponentsResult::components)
+      .def_readonly("largest_label", &ComponentsResult::largest_label)
+      .def_readonly("largest_size", &ComponentsResult::largest_size)
+      .def_readonly("singletons", &ComponentsResult::singletons)
+      .def_readonly("ms", &ComponentsResult::ms)
+      .def_readonly("link_ms", &ComponentsResult::link_ms)
+      .def_readonly("compress_ms", &ComponentsResult::compress_ms)
+      .def_readonly("sampled", &ComponentsResult::sampled);
+
   py::class_<Engine, std::shared_ptr<Engine>>(m, "Engine")
       .def(py::init([](std::shared_ptr<DeviceGraph> g, std::shared_ptr<Comm> c, const std::string& mode, double alpha,
                        double beta, int bu_lane_limit, bool phase_timing, bool force_exchange) {
@@ -865,6 +887,37 @@ PYBIND11_MODULE(_dbfs_native, m) {
              return py::make_tuple(mant, exp);
            })
       .def("build_in_edges", &Engine::build_in_edges, py::call_guard<py::gil_scoped_release>())
+      // connected components (sample_entries < 0: the engine option cc_sample_entries)
+      .def(
+          "components",
+          [](Engine& e, int64_t sample_entries) {
+            ComponentsOptions o;
+            o.sample_entries = sample_entries;
+            py::gil_scoped_release rel;
+            return e.components(o);
+          },
+          py::arg("sample_entries") = -1)
+      .def_property_readonly("has_components", &Engine::has_components)
+      .def("last_components", [](const Engine& e) { return e.last_components(); })
+      // the last components() call's labels / per-vertex component sizes: int64 [n]
+      .def("gather_components",
+           [](Engine& e) {
+             std::vector<int64_t> v;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_components();
+             }
+             return to_numpy(v);
+           })
+      .def("gather_component_sizes",
+           [](Engine& e) {
+             std::vector<int64_t> v;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_component_sizes();
+             }
+             return to_numpy(v);
+           })
       .def("gather_batch_parents",
            [](Engine& e) {
              std::vector<int64_t> v;

@@ -116,6 +116,30 @@ class BatchResult:
                 f"gteps={self.gteps:.2f})")
 
 
+class ComponentsResult:
+    """Connected components of the whole graph (``BFS.components``):
+    ``components`` (how many), ``largest_label`` / ``largest_size`` (the
+    largest one: its smallest vertex id and its vertex count; the smaller
+    label on a tie), ``singletons`` (components of one vertex: no entries, or
+    only self-loops), ``ms`` (wall time, max over ranks) with its ``link_ms``
+    (hook launches; several ranks: the label exchange too) and ``compress_ms``
+    (pointer jumping) parts, and ``sampled``: the sample-and-skip form ran
+    (one rank, undirected, a non-zero ``sample_entries``)."""
+
+    __slots__ = ("components", "largest_label", "largest_size", "singletons", "ms", "link_ms", "compress_ms", "sampled")
+
+    def __init__(self, r: Any):
+        self.components, self.singletons = int(r.components), int(r.singletons)
+        self.largest_label, self.largest_size = int(r.largest_label), int(r.largest_size)
+        self.ms, self.link_ms, self.compress_ms = float(r.ms), float(r.link_ms), float(r.compress_ms)
+        self.sampled = bool(r.sampled)
+
+    def __repr__(self) -> str:
+        return (f"ComponentsResult(components={self.components}, largest_label={self.largest_label}, "
+                f"largest_size={self.largest_size}, singletons={self.singletons}, ms={self.ms:.4f}, "
+                f"sampled={self.sampled})")
+
+
 class BFS:
     """Distributed BFS over a graph given as a HostCSR, generator params, or a file path."""
 
@@ -344,8 +368,59 @@ class BFS:
             d = self.graph.degrees_of([int(v) - self.partition.lo(own)])[0]
         return int(self.rt.comm.sum_host(int(d))) if self.rt.world > 1 else int(d)
 
-    def sample_roots(self, k: int, seed: int = 1) -> List[int]:
-        """Graph500 root sampling: k distinct random vertices of degree >= 1 (collective)."""
+    def components(self, sample_entries: Optional[int] = None) -> ComponentsResult:
+        """Connected components of the whole graph on the device (collective):
+        label[v] = the smallest vertex id of v's component; on a directed
+        graph the weakly connected components.  A hook-and-compress forest
+        over the adjacency (one pass over the entries, then pointer jumping),
+        not a traversal per component.  ``sample_entries`` (default: the
+        engine option ``cc_sample_entries``, 2): on one rank of an undirected
+        graph only that many entries of every row are hooked first, and the
+        rows of the component most of a vertex sample then lies in are skipped
+        in the pass over the rest; 0 links every entry in one pass, which
+        directed graphs and several ranks always do.  The labels are the same
+        either way.  Several ranks exchange whole label arrays: correct, not
+        fast.  8 bytes per vertex of the whole graph on the device, kept; the
+        state of run / run_batch / validate is left alone."""
+        return ComponentsResult(self.engine.components(-1 if sample_entries is None else int(sample_entries)))
+
+    def component_labels(self) -> np.ndarray:
+        """Labels of the last components() as int64 [n]."""
+        return self.engine.gather_components()
+
+    def component_sizes(self) -> np.ndarray:
+        """int64 [n]: entry v is the number of vertices in v's component (last components())."""
+        return self.engine.gather_component_sizes()
+
+    def _component_roots(self, k: int, seed: int, component) -> List[int]:
+        if not self.engine.has_components:
+            self.components()
+        if isinstance(component, str):
+            if component != "largest":
+                raise ValueError('component must be None, "largest" or a component label')
+            label = int(self.engine.last_components().largest_label)
+        else:
+            label = int(component)
+        members = np.nonzero(self.component_labels() == label)[0]
+        roots: List[int] = []
+        if members.size >= k:
+            for v in np.random.default_rng(seed).permutation(members):
+                if len(roots) == k:
+                    break
+                if self.degree(int(v)) > 0:
+                    roots.append(int(v))
+        if len(roots) < k:
+            raise ValueError(f"component {label} has fewer than {k} vertices of degree >= 1")
+        return roots
+
+    def sample_roots(self, k: int, seed: int = 1, component=None) -> List[int]:
+        """Graph500 root sampling: k distinct random vertices of degree >= 1 (collective).
+        ``component="largest"`` samples them from the largest connected
+        component (running components() first if it has not run), an int from
+        the component with that label; raises ValueError when the component
+        has fewer than k vertices of degree >= 1."""
+        if component is not None:
+            return self._component_roots(int(k), seed, component)
         rng = np.random.default_rng(seed)
         roots: List[int] = []
         seen = set()

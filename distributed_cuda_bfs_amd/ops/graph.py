@@ -81,6 +81,13 @@ def cpu_bfs(csr, src: int):
     return N.cpu_bfs(csr, int(src))
 
 
+def cpu_components(csr):
+    """Sequential connected-components oracle (union-find): int64 [n], label[v]
+    = the smallest vertex id of v's component, every stored entry joining its
+    two ends (a directed CSR: the weakly connected components)."""
+    return N.cpu_components(csr)
+
+
 def cpu_betweenness(csr, sources, directed: bool = False, path_counts: bool = False, wide_counts: bool = False):
     """Sequential Brandes oracle over the stored adjacency entries (duplicates
     are parallel edges, self-loops never lie on a shortest path): returns

@@ -142,3 +142,32 @@ def parents_are_valid(csr, levels, parents, src: int) -> bool:
         if p not in col[ro[v]:ro[v + 1]]:
             return False
     return True
+
+
+def component_labels_reference(csr) -> np.ndarray:
+    """Connected-component labels by numpy min-label propagation, int64[n]:
+    label[v] = the smallest vertex id of v's component, every stored entry
+    u -> w joining u and w (a directed CSR: weak connectivity).  Each round
+    gives both ends of every entry the smaller of their labels and then jumps
+    every pointer to its label's label until nothing moves; labels only fall,
+    so the fixed point is the component minimum.  O(log n) rounds on the
+    graphs of the tests; independent of cpu_components and of the backends."""
+    ro = np.asarray(csr.row_off)
+    w = np.asarray(csr.col).astype(np.int64)
+    n = int(csr.n)
+    u = np.repeat(np.arange(n, dtype=np.int64), np.diff(ro))
+    label = np.arange(n, dtype=np.int64)
+    while True:
+        low = np.minimum(label[u], label[w])
+        new = label.copy()
+        # hook the labels themselves (the roots), not only the two vertices
+        np.minimum.at(new, label[u], low)
+        np.minimum.at(new, label[w], low)
+        while True:
+            nxt = new[new]
+            if np.array_equal(nxt, new):
+                break
+            new = nxt
+        if np.array_equal(new, label):
+            return label
+        label = new
