@@ -39,12 +39,17 @@ HEADERS   := $(wildcard csrc/include/dbfs/*.hpp) $(wildcard csrc/kernels/*.hpp) 
 all: $(CLI) $(PYMOD) bin/bfs_checked
 lib: $(CORE_LIB)
 
-# Device-checked build: bin/bfs_checked, the traversal kernels
-# built with -DDBFS_CHECKED (work-list, owner-list and vertex-id bounds
-# verified on the device; the first violation fails the run on the host,
-# HipBackend::take_device_check).  Host code and the other kernels unchanged.
+# Device-checked build: bin/bfs_checked, every kernel file with
+# DBFS_DCHECK sites built with -DDBFS_CHECKED: the traversal, batch,
+# betweenness, components and graph-build (in-edge routing) kernels verify
+# the bounds of their work lists, owner lists, rows and vertex ids on the
+# device; the first violation fails the run on the host, named with its file
+# (HipBackend::take_device_check).  CHECKED_SRC lists every such file (one
+# line: tests/test_checked_build.py reads it); the binary calls itself
+# +checked only when all of them compiled their sites.  Host code and the
+# kernel files without sites (ref_kernels, graph_sort, peer_kernels) unchanged.
 CHECKED_BUILD := build-checked
-CHECKED_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip
+CHECKED_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/ms_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip csrc/kernels/graph_kernels.hip
 CHECKED_OBJ   := $(patsubst csrc/%.hip,$(CHECKED_BUILD)/%.o,$(CHECKED_SRC))
 checked: bin/bfs_checked
 $(CHECKED_BUILD)/%.o: csrc/%.hip $(HEADERS)

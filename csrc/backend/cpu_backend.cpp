@@ -120,6 +120,8 @@ class CpuBackend final : public Backend {
           const int b = __builtin_ctzll(x);
           x &= x - 1;
           const int64_t v = w * 64 + b;
+          // (padding bits are pre-set visited; a forced update takes its level bytes unmasked)
+          DBFS_CHECK(v < a.g.rows, "update: a new vertex in the last word's padding");
           a.out.store(v);
           const eid_t d = a.g.row_off[v + 1] - a.g.row_off[v];
           if (d > 0) { ++cnt; deg += d; }
@@ -140,6 +142,10 @@ class CpuBackend final : public Backend {
         if (a.out.level8) a.out.level8[i] = i == src ? a.out.narrow_base : kNarrowUnreached;
         else a.out.level[i] = i == src ? 0 : kUnreached;
       }
+      // (the last word's padding bytes too: a split level's forced update
+      // takes every byte equal to its level as a new vertex, unmasked)
+      if (a.out.level8)
+        for (int64_t i = a.g.rows; i < a.words * kWordBits; ++i) a.out.level8[i] = kNarrowUnreached;
     }
     for (int64_t w = 0; w < a.gwords; ++w) a.visited[w] = a.zdeg[w];
     if (a.frontier_clean && !a.frontier_global) {
@@ -735,10 +741,18 @@ class CpuBackend final : public Backend {
   int64_t sparse_cnt_ = 0, sparse_deg_ = 0;  // the current sparse level's settled entries / their edges
 
   // (no device checks in the CPU kernels; the injected violation exercises
-  // the engine's failure path on the CPU)
-  uint64_t take_device_check() override { return std::exchange(check_, 0); }
-  void inject_device_check() override { check_ = 99ull << 48; }
+  // the engine's failure path on the CPU: one word, reported with the file
+  // the injection named)
+  uint64_t take_device_check(CheckFile* file) override {
+    if (file) *file = check_file_;
+    return std::exchange(check_, 0);
+  }
+  void inject_device_check(CheckFile f) override {
+    check_ = 99ull << 48;
+    check_file_ = f;
+  }
   uint64_t check_ = 0;
+  CheckFile check_file_ = CheckFile::Bfs;
 
   void list_scatter(const ListScatterArgs& a) override {
     for (int r = 0; r < a.nranks; ++r) {

@@ -294,15 +294,15 @@ class HipBackend final : public Backend {
   void pack_bytes(const PackArgs& a) override { on(); kern::pack_bytes(a, st_); chk(); }
   void list_scatter(const ListScatterArgs& a) override { on(); kern::list_scatter(a, st_); chk(); }
   bool device_checks_enabled() const override { return kern::checks_enabled(); }
-  uint64_t take_device_check() override {
+  uint64_t take_device_check(CheckFile* file) override {
     // (only the checked build has a word to read: otherwise no synchronize --
     // a traversal's speculative trailing chain keeps draining while the next
     // one is enqueued behind it)
     if (!kern::checks_enabled()) return 0;
     synchronize();
-    return kern::take_check_error();
+    return kern::take_check_error(file);
   }
-  void inject_device_check() override { on(); kern::inject_check_failure(st_); chk(); }
+  void inject_device_check(CheckFile f) override { on(); kern::inject_check_failure(f, st_); chk(); }
   void bu_step(const BuArgs& a) override { on(); kern::bu_step(a, st_); chk(); }
   void hub_gather(const HubGatherArgs& a) override { on(); kern::hub_gather(a, st_); chk(); }
   void bu_cut_prep(const BuArgs& a) override { on(); kern::bu_cut_prep(a, st_); chk(); }

@@ -77,6 +77,7 @@ struct Args {
   std::string components_out;         // ... the labels, one per line
   int64_t cc_sample_entries = -1;     // --cc-sample-entries N (EngineOptions::cc_sample_entries; -1: the default)
   bool mode_given = false;            // --mode on the command line (--directed turns only the default into td)
+  std::vector<std::pair<std::string, double>> opts;  // --opt name=value, in order (set_engine_option)
 };
 
 [[noreturn]] void usage(const char* msg = nullptr) {
@@ -101,7 +102,13 @@ struct Args {
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only; --batch and --validate work on the in-edge shard,\n"
                "                   built on the device on first use)\n"
-               "       --level-csv FILE (per-level records of every run: root,level,dir,frontier,...,ms)\n");
+               "       --level-csv FILE (per-level records of every run: root,level,dir,frontier,...,ms)\n"
+               "       --opt NAME=VALUE (repeatable: an engine option by name, a number, applied after the flags above,\n"
+               "                   e.g. td_bin_edges=1, device_loop=0; an unknown name or a value that is no number is an\n"
+               "                   error)\n"
+               "       --json lines of a run carry \"chains\": every level chain the device loop enqueued, in order, as\n"
+               "                   {l, form (T dense, S sparse, X binned top-down; B bottom-up), unvis, split, cut};\n"
+               "                   [] with the host loop\n");
   std::exit(2);
 }
 
@@ -156,6 +163,22 @@ Args parse(int argc, char** argv) {
     else if (s == "--phase-timing") a.phase_timing = true;
     else if (s == "--no-hub-sort") a.hub_sort = false;
     else if (s == "--directed") a.directed = true;
+    else if (s == "--opt") {
+      const std::string kv = next();
+      const size_t eq = kv.find('=');
+      if (eq == std::string::npos || eq == 0 || eq + 1 == kv.size()) usage(("--opt expects NAME=VALUE, got " + kv).c_str());
+      const std::string name = kv.substr(0, eq), val = kv.substr(eq + 1);
+      char* end = nullptr;
+      const double v = std::strtod(val.c_str(), &end);
+      if (!end || *end || !std::isfinite(v)) usage(("--opt " + name + ": value is not a number: " + val).c_str());
+      try {
+        EngineOptions probe;
+        set_engine_option(probe, name, v);
+      } catch (const std::exception& e) {
+        usage(("--opt: " + std::string(e.what())).c_str());
+      }
+      a.opts.emplace_back(name, v);
+    }
     else if (s == "-h" || s == "--help") usage();
     else if (!s.empty() && s[0] == '-' && s.size() > 1 && !std::isdigit(static_cast<unsigned char>(s[1])))
       usage(("unknown flag " + s).c_str());
@@ -272,6 +295,15 @@ std::string json_run(const RunResult& r, const std::string& graph, int64_t n, in
     s += "{\"l\":" + std::to_string(l.level) + ",\"dir\":\"" + std::string(1, l.direction) +
          "\",\"frontier\":" + std::to_string(l.frontier) + ",\"edges\":" + std::to_string(l.frontier_edges) +
          ",\"new\":" + std::to_string(l.discovered) + ",\"ms\":" + std::to_string(l.ms) + "}";
+  }
+  // every chain the device loop enqueued, in order (ChainRecord; none with the host loop)
+  s += "],\"chains\":[";
+  for (size_t i = 0; i < r.chains.size(); ++i) {
+    const auto& c = r.chains[i];
+    if (i) s += ",";
+    s += "{\"l\":" + std::to_string(c.level) + ",\"form\":\"" + std::string(1, c.form) +
+         "\",\"unvis\":" + (c.unvis ? "true" : "false") + ",\"split\":" + std::to_string(c.split) +
+         ",\"cut\":" + (c.cut ? "true" : "false") + "}";
   }
   return s + "]}";
 }
@@ -541,6 +573,7 @@ int main(int argc, char** argv) {
     eo.phase_timing = a.phase_timing;
     eo.directed = a.directed;
     if (a.cc_sample_entries >= 0) eo.cc_sample_entries = a.cc_sample_entries;
+    for (const auto& kv : a.opts) set_engine_option(eo, kv.first, kv.second);
     run_ranks(ranks, [&](int i, RankCtx& rc) {
       const int rk = multiproc ? wrank : i;
       if (synth) rc.graph = DeviceGraph::generate(*rc.be, gp, part, rk);

@@ -557,7 +557,7 @@ void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bo
       ++out.bc_launches;
     }
     if (a.wide) break;  // (no count leaves the wide range)
-    if (fault_.kind == "bc_device" && fault_.rank == comm_.rank()) be_.inject_device_check();
+    if (fault_.kind == "bc_device" && fault_.rank == comm_.rank()) be_.inject_device_check(CheckFile::MsBc);
     // A count past DBL_MAX is inf, and the backward sweep's inf * 0 would be
     // NaN: the batch fails here, on every rank, before a count is copied out
     // (Auto: the pass starts again in the wide form, on every rank).
@@ -573,7 +573,7 @@ void Engine::bc_batch_pass(const MsPassMatrix& m, int depth, bool accumulate, bo
   if (a.wide) {
     ++out.wide_count_passes;
     if (form == BatchCounts::Wide && fault_.kind == "bc_device" && fault_.rank == comm_.rank())
-      be_.inject_device_check();
+      be_.inject_device_check(CheckFile::MsBc);
   }
   if (counts) {
     const size_t at = static_cast<size_t>(first) * static_cast<size_t>(n);

@@ -78,7 +78,7 @@ ComponentsResult Engine::components(const ComponentsOptions& o) {
     a.first = 0;
     a.count = res.sampled ? sample : -1;
     be_.cc_link(a);
-    if (fault_.kind == "cc_device" && fault_.rank == comm_.rank()) be_.inject_device_check();
+    if (fault_.kind == "cc_device" && fault_.rank == comm_.rank()) be_.inject_device_check(CheckFile::Cc);
   });
   timed(compress_ms, [&] { be_.cc_compress(a); });
   if (res.sampled) {

@@ -346,7 +346,7 @@ void DeviceGraph::build_in_edges(Comm& comm) {
   has_in_edges_ = true;
   // checked build: a bounds violation of the build's kernels fails it here
   const FaultSpec fault = FaultSpec::from_env();
-  if (fault.kind == "in_edges_device" && fault.rank == rank_) be.inject_device_check();
+  if (fault.kind == "in_edges_device" && fault.rank == rank_) be.inject_device_check(CheckFile::Graph);
   throw_device_check(be, rank_);
 }
 
@@ -686,7 +686,10 @@ void Engine::read_level_stats(int64_t* host_stats) {
 // at the start of level L of every run: `throw` raises an Error (in-process
 // ranks abort their group), `exit` ends the process with status 17 (a crashed
 // rank), `hang` stops participating (peers must time out), `device` records
-// a device-check violation (the run fails when it ends), `batch_device` the
+// a device-check violation (the run fails when it ends; file=td_kernels or
+// file=bu_kernels: in that kernel file's word instead of bfs_kernels'; every
+// other *_device kind records in the word of the file its phase's kernels
+// live in: ms_kernels, ms_bc_kernels, cc_kernels, graph_kernels), `batch_device` the
 // same at level L of a batch pass (run_batch fails after the pass), `bc_device`
 // the same during a pass's dependency accumulation (run_batch(betweenness)
 // fails after it), `cc_device` the same during the link of components()
@@ -702,6 +705,7 @@ FaultSpec FaultSpec::from_env() {
   if (!e || !*e) return f;
   std::string s(e);
   size_t pos = 0;
+  bool file_given = false;
   while (pos < s.size()) {
     size_t comma = s.find(',', pos);
     if (comma == std::string::npos) comma = s.size();
@@ -714,6 +718,12 @@ FaultSpec FaultSpec::from_env() {
     else if (k == "kind") f.kind = v;
     else if (k == "ms") f.ms = std::stoi(v);
     else if (k == "us") f.us = std::stoi(v);
+    else if (k == "file") {
+      DBFS_CHECK(v == "bfs_kernels" || v == "td_kernels" || v == "bu_kernels",
+                 "DBFS_FAULT_INJECT: file must be bfs_kernels|td_kernels|bu_kernels");
+      f.file = v == "td_kernels" ? CheckFile::Td : v == "bu_kernels" ? CheckFile::Bu : CheckFile::Bfs;
+      file_given = true;
+    }
     else DBFS_CHECK(false, "DBFS_FAULT_INJECT: unknown key '" + k + "'");
     pos = comma + 1;
   }
@@ -722,6 +732,7 @@ FaultSpec FaultSpec::from_env() {
                  f.kind == "in_edges_device" || f.kind == "bc_device" || f.kind == "cc_device",
              "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|bc_device|cc_device|in_edges_device|delay|rccl_init|"
              "peer_init|late_wg");
+  DBFS_CHECK(!file_given || f.kind == "device", "DBFS_FAULT_INJECT: file applies to kind=device only");
   // (rccl_init / peer_init: the communicators' setup fails -- NcclComm /
   // PeerComm read them; late_wg: every sparse top-down level's ticket-less
   // workgroups start late, on every rank (DeviceLoop::emit_sparse) -- the
@@ -735,19 +746,23 @@ FaultSpec FaultSpec::from_env() {
 // the kernel files).  Read after every traversal, every batch pass and its
 // check, every single-source validation / parent tree and the in-edge build;
 // without the checked build there is no word to read and nothing is waited for.
+// Two files may use one code: the message names the file whose word held it.
 static void throw_device_check(Backend& be, int rank) {
-  const uint64_t v = be.take_device_check();
+  CheckFile file = CheckFile::Bfs;
+  const uint64_t v = be.take_device_check(&file);
   if (v == 0) return;
-  char buf[160];
-  std::snprintf(buf, sizeof(buf), "device check failed on rank %d: code %llu, detail %llu", rank,
-                static_cast<unsigned long long>(v >> 48), static_cast<unsigned long long>(v & 0xFFFFFFFFFFFFull));
+  char buf[200];
+  std::snprintf(buf, sizeof(buf), "device check failed on rank %d: code %llu, detail %llu, file %s", rank,
+                static_cast<unsigned long long>(v >> 48), static_cast<unsigned long long>(v & 0xFFFFFFFFFFFFull),
+                check_file_name(file));
   throw Error(buf);
 }
 
 void Engine::check_device() { throw_device_check(be_, comm_.rank()); }
 
 void Engine::inject_batch_fault(int level) {
-  if (fault_.kind == "batch_device" && fault_.rank == comm_.rank() && fault_.level == level) be_.inject_device_check();
+  if (fault_.kind == "batch_device" && fault_.rank == comm_.rank() && fault_.level == level)
+    be_.inject_device_check(CheckFile::Ms);
 }
 
 void Engine::inject_fault(int level) {
@@ -758,7 +773,7 @@ void Engine::inject_fault(int level) {
   if (fault_.kind == "device") {
     // a kernel-side bounds violation (recorded, not raised: the traversal
     // completes and Engine::check_device fails it afterwards)
-    be_.inject_device_check();
+    be_.inject_device_check(fault_.file);
     return;
   }
   if (fault_.kind == "delay") {

@@ -29,6 +29,17 @@ namespace dbfs {
 
 enum class DeviceKind { CPU, HIP };
 
+// Device-checked build: the kernel files that record bounds violations, each
+// in a word of its own (the codes of two files may coincide: a violation is
+// reported with its file).
+enum class CheckFile { Bfs, Td, Bu, Ms, MsBc, Cc, Graph };
+constexpr int kCheckFiles = 7;
+inline const char* check_file_name(CheckFile f) {
+  constexpr const char* names[kCheckFiles] = {"bfs_kernels", "td_kernels",  "bu_kernels",   "ms_kernels",
+                                              "ms_bc_kernels", "cc_kernels", "graph_kernels"};
+  return names[static_cast<int>(f)];
+}
+
 // ---- kernel argument blocks -------------------------------------------------
 
 // Local CSR shard: rows [lo, lo + rows) of an n-vertex graph, global column ids.
@@ -1447,10 +1458,12 @@ class Backend {
   virtual void refresh_visited(const RefreshArgs& a) = 0;
   // Device-checked build (make checked): whether the kernels verify their
   // bounds, the first recorded violation (code << 48 | detail; 0: none;
-  // synchronises, clears), and a hook recording violation 99 (fault tests).
+  // synchronises, clears; *file: the kernel file whose word held it), and a
+  // hook recording violation 99 in that file's word (fault tests).  Enabled
+  // means every kernel file with check sites compiled them.
   virtual bool device_checks_enabled() const { return false; }
-  virtual uint64_t take_device_check() { return 0; }
-  virtual void inject_device_check() {}
+  virtual uint64_t take_device_check(CheckFile* file = nullptr) { (void)file; return 0; }
+  virtual void inject_device_check(CheckFile file = CheckFile::Bfs) { (void)file; }
   virtual void status_expand(const StatusArgs& a) = 0;
   virtual void bitmap_or(word_t* dst, const word_t* src, int64_t words) = 0;
   virtual void ref_expand(const RefExpandArgs& a) = 0;

@@ -556,6 +556,7 @@ struct FaultSpec {
   std::string kind = "throw";  // FaultSpec::from_env lists the kinds
   int ms = 2000;  // kind=delay: how long the rank sleeps before enqueueing the level
   int us = 500;   // kind=late_wg: how long td_sparse's ticket-less workgroups wait (TdSparseArgs::late_ticks)
+  CheckFile file = CheckFile::Bfs;  // kind=device: the kernel file whose word records it (file=td_kernels|bu_kernels)
   static FaultSpec from_env();
 };
 

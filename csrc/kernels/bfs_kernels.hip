@@ -99,7 +99,12 @@ __global__ __launch_bounds__(kBlock) void init_run_kernel(InitRunArgs a) {
       }
       l16[i] = v;
     }
-    for (int64_t i = n16 * 16 + t0; i < rows; i += stride) a.out.level8[i] = i == src ? a.out.narrow_base : kNarrowUnreached;
+    // (the tail, and the last word's padding bytes: a split level's forced
+    // update takes every byte equal to its level as a new vertex, unmasked --
+    // a stale byte there was a vertex past the rows, its degree read off the
+    // end of row_off)
+    for (int64_t i = n16 * 16 + t0; i < a.words * kWordBits; i += stride)
+      a.out.level8[i] = i == src ? a.out.narrow_base : kNarrowUnreached;
   } else {
     // level: rows / 4 int4 stores (+ tail)
     const int64_t n4 = (reinterpret_cast<uintptr_t>(a.out.level) & 15u) == 0 ? rows / 4 : 0;
@@ -267,6 +272,8 @@ __device__ __forceinline__ void update_unit(const UpdateArgs& a, int64_t unit, b
     }
     const word_t vis = a.visited[wl];
     nb = a.force ? c : (c & ~vis);
+    // (no new vertex in the last word's padding: its degree would be read past row_off)
+    DBFS_DCHECK(!nb || wl * 64 + (63 - __clzll(static_cast<long long>(nb))) < a.g.rows, 16, wl);
     if (nb) a.visited[wl] = vis | nb;
     a.frontier[wl] = nb;
     if constexpr (kRanks) {
@@ -754,32 +761,34 @@ int device_cus() {
   return cus[dev];
 }
 
-#ifdef DBFS_CHECKED
-__global__ void check_fail_kernel(unsigned long long code) { DBFS_DCHECK(false, code, 0); }
-#endif
-
-void inject_check_failure(hipStream_t st) {
-#ifdef DBFS_CHECKED
-  check_fail_kernel<<<1, 1, 0, st>>>(99);
-#else
-  (void)st;
-#endif
+// Fault tests' hook: violation 99 in the word of the file asked for.
+void inject_check_failure(CheckFile f, hipStream_t st) {
+  switch (f) {
+    case CheckFile::Bfs: inject_check_local(st); break;
+    case CheckFile::Td: inject_check_td(st); break;
+    case CheckFile::Bu: inject_check_bu(st); break;
+    case CheckFile::Ms: inject_check_ms(st); break;
+    case CheckFile::MsBc: inject_check_ms_bc(st); break;
+    case CheckFile::Cc: inject_check_cc(st); break;
+    case CheckFile::Graph: inject_check_graph(st); break;
+  }
 }
 
+// Every kernel file that records violations compiled its check sites (a
+// checked build that leaves one out is not a checked build).
 bool checks_enabled() {
-#ifdef DBFS_CHECKED
-  return true;
-#else
-  return false;
-#endif
+  return kCheckedLocal && kCheckedTd && kCheckedBu && kCheckedMs && kCheckedMsBc && kCheckedCc && kCheckedGraph;
 }
 
-unsigned long long take_check_error() {
+unsigned long long take_check_error(CheckFile* file) {
   // (each kernel file records into its own g_check; all are read and cleared)
-  const unsigned long long h[7] = {take_check_local(), take_check_td(), take_check_bu(), take_check_ms(),
-                                   take_check_ms_bc(), take_check_cc(), take_check_graph()};
-  for (unsigned long long x : h)
-    if (x) return x;
+  const unsigned long long h[kCheckFiles] = {take_check_local(), take_check_td(), take_check_bu(), take_check_ms(),
+                                             take_check_ms_bc(), take_check_cc(), take_check_graph()};
+  for (int i = 0; i < kCheckFiles; ++i)
+    if (h[i]) {
+      if (file) *file = static_cast<CheckFile>(i);
+      return h[i];
+    }
   return 0;
 }
 

@@ -1176,6 +1176,8 @@ void hub_gather(const HubGatherArgs& a, hipStream_t st) {
 }
 
 unsigned long long take_check_bu() { return take_check_local(); }
+void inject_check_bu(hipStream_t st) { inject_check_local(st); }
+const bool kCheckedBu = kCheckedLocal;
 
 }  // namespace kern
 }  // namespace dbfs

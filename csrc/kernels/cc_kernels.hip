@@ -338,6 +338,8 @@ void cc_sizes(const CcArgs& a, hipStream_t st) {
 }
 
 unsigned long long take_check_cc() { return take_check_local(); }
+void inject_check_cc(hipStream_t st) { inject_check_local(st); }
+const bool kCheckedCc = kCheckedLocal;
 
 }  // namespace kern
 }  // namespace dbfs

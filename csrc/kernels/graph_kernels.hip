@@ -480,6 +480,8 @@ void entries_fill(const uint64_t* e, int64_t k, int64_t lo, eid_t* cursor, vid_t
 int route_max_ranks() { return kMaxRouteRanks; }
 
 unsigned long long take_check_graph() { return take_check_local(); }
+void inject_check_graph(hipStream_t st) { inject_check_local(st); }
+const bool kCheckedGraph = kCheckedLocal;
 
 int64_t scan_tmp_elems(int64_t n) {
   int64_t total = 0;

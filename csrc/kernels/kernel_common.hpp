@@ -18,13 +18,22 @@ namespace kern {
 
 // Checked build: the first violation recorded by the top-down / bottom-up
 // kernel files, the batch kernels and the graph-build kernels (cleared);
-// bfs_kernels.hip's take_check_error reads them all.
+// bfs_kernels.hip's take_check_error reads them all.  Next to each: the test
+// hook recording code 99 in that file's word, and whether the file compiled
+// its check sites (checks_enabled: all of them did).
 unsigned long long take_check_td();
 unsigned long long take_check_bu();
 unsigned long long take_check_ms();
 unsigned long long take_check_ms_bc();
 unsigned long long take_check_cc();
 unsigned long long take_check_graph();
+void inject_check_td(hipStream_t st);
+void inject_check_bu(hipStream_t st);
+void inject_check_ms(hipStream_t st);
+void inject_check_ms_bc(hipStream_t st);
+void inject_check_cc(hipStream_t st);
+void inject_check_graph(hipStream_t st);
+extern const bool kCheckedTd, kCheckedBu, kCheckedMs, kCheckedMsBc, kCheckedCc, kCheckedGraph;
 // A level's totals and finish from unscanned unit statistics, one workgroup
 // (bfs_kernels.hip; bottom-up levels without the fused finish).
 void totals_finish(const ScanArgs& a, hipStream_t st);
@@ -421,6 +430,18 @@ inline unsigned long long take_check_local() {
   return 0;
 #endif
 }
+
+// Whether this file's check sites are compiled, and the fault tests' hook: one
+// thread records violation 99 in this file's word (a recorded word like any
+// site's -- no trap; the kernels around it run on).
+#ifdef DBFS_CHECKED
+constexpr bool kCheckedLocal = true;
+__global__ void check_fail_kernel(unsigned long long code) { DBFS_DCHECK(false, code, 0); }
+inline void inject_check_local(hipStream_t st) { check_fail_kernel<<<1, 1, 0, st>>>(99); }
+#else
+constexpr bool kCheckedLocal = false;
+inline void inject_check_local(hipStream_t) {}
+#endif
 
 }  // namespace
 }  // namespace kern

@@ -50,12 +50,13 @@ void hub_visited(const HubVisitedArgs& a, hipStream_t st);
 void unvis_filter(const UnvisArgs& a, hipStream_t st);
 void hub_apply(const HubApplyArgs& a, hipStream_t st);
 void refresh_visited(const RefreshArgs& a, hipStream_t st);
-// device-checked build (DBFS_CHECKED): whether checks are compiled in, the
-// first recorded violation (code << 48 | detail, 0: none; cleared), and a
-// test hook recording code 99
+// device-checked build (DBFS_CHECKED): whether every kernel file that records
+// violations compiled its checks in; the first recorded violation (code << 48
+// | detail, 0: none; cleared; *file: whose word held it); and a test hook
+// recording code 99 in the word of `f`
 bool checks_enabled();
-unsigned long long take_check_error();
-void inject_check_failure(hipStream_t st);
+unsigned long long take_check_error(CheckFile* file);
+void inject_check_failure(CheckFile f, hipStream_t st);
 void status_expand(const StatusArgs& a, hipStream_t st);
 void bitmap_or(word_t* dst, const word_t* src, int64_t words, hipStream_t st);
 void copy_pieces(const Backend::CopyPieces& c, hipStream_t st);

@@ -333,6 +333,8 @@ void ms_bc_long_rows(const eid_t* row_off, int64_t rows, int64_t above, vid_t* l
 }
 
 unsigned long long take_check_ms_bc() { return take_check_local(); }
+void inject_check_ms_bc(hipStream_t st) { inject_check_local(st); }
+const bool kCheckedMsBc = kCheckedLocal;
 
 }  // namespace kern
 }  // namespace dbfs

@@ -520,6 +520,8 @@ void ms_check(const MsCheckArgs& a, hipStream_t st) {
 }
 
 unsigned long long take_check_ms() { return take_check_local(); }
+void inject_check_ms(hipStream_t st) { inject_check_local(st); }
+const bool kCheckedMs = kCheckedLocal;
 
 void ms_init(const MsInitArgs& a, hipStream_t st) {
   ms_level_type(a.s.lvl_bytes, [&](auto l) { ms_init_kernel<decltype(l)><<<1, kWave, 0, st>>>(a); });

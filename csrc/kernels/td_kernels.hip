@@ -1592,6 +1592,8 @@ void hub_apply(const HubApplyArgs& a, hipStream_t st) {
 }
 
 unsigned long long take_check_td() { return take_check_local(); }
+void inject_check_td(hipStream_t st) { inject_check_local(st); }
+const bool kCheckedTd = kCheckedLocal;
 
 }  // namespace kern
 }  // namespace dbfs

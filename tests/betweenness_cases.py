@@ -344,6 +344,7 @@ def cli_checked_reports(bfs_checked, path):
     out = subprocess.run([bfs_checked] + flags, capture_output=True, text=True, timeout=120, env=env)
     assert out.returncode != 0, out.stdout
     assert "device check failed on rank 0: code 99" in out.stderr, out.stderr[-2000:]
+    assert "file ms_bc_kernels" in out.stderr, out.stderr[-2000:]
     assert "batch betweenness" not in out.stdout
     out = dc.run_cli(bfs_checked, flags)
     assert out.returncode == 0, out.stdout + out.stderr

@@ -427,6 +427,7 @@ def cli_checked_reports(bfs_checked):
     out = run_cli(bfs_checked, flags, env=dict(os.environ, DBFS_FAULT_INJECT="rank=0,kind=cc_device"))
     assert out.returncode != 0, out.stdout
     assert "device check failed on rank 0: code 99" in out.stderr, out.stderr[-2000:]
+    assert "file cc_kernels" in out.stderr, out.stderr[-2000:]
     assert "components 1718" not in out.stdout
 
 

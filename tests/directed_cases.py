@@ -479,11 +479,13 @@ def cli_checked_reports(bfs_checked, path):
     """bin/bfs_checked: the batch (which builds the in-edge shard) fails on the
     recorded violation, which the single run from <src> before it does not see."""
     flags = ["0", path, "--directed", "--roots", "70", "--batch", "--validate"]
-    for inject in ("rank=0,kind=in_edges_device", "rank=0,level=1,kind=batch_device"):
+    for inject, file in (("rank=0,kind=in_edges_device", "graph_kernels"),
+                         ("rank=0,level=1,kind=batch_device", "ms_kernels")):
         env = dict(os.environ, DBFS_FAULT_INJECT=inject)
         out = subprocess.run([bfs_checked] + flags, capture_output=True, text=True, timeout=120, env=env)
         assert out.returncode != 0, out.stdout
         assert "device check failed on rank 0: code 99" in out.stderr, out.stderr[-2000:]
+        assert "file " + file in out.stderr, out.stderr[-2000:]  # (the word of the file whose kernels ran)
         assert "batch validation" not in out.stdout
     out = run_cli(bfs_checked, flags)
     assert out.returncode == 0, out.stdout + out.stderr
