@@ -473,6 +473,91 @@ class CpuBackend final : public Backend {
     a.totals[2] = best;
     a.totals[3] = best_label;
   }
+  // strongly connected components (SccArgs): the device's sweeps as plain
+  // loops, in place (a later row sees what an earlier one stored: the device's
+  // "may read entries written earlier in the same launch")
+  static bool scc_counts(const SccArgs& a, vid_t v, vid_t w) {
+    return w != v && a.cls[w] == a.cls[v] && a.scc[w] == kSccNone;
+  }
+  void scc_init(const SccArgs& a) override {
+    for (int64_t v = 0; v < a.out.n; ++v) a.scc[v] = a.cls[v] = a.colour[v] = kSccNone;
+  }
+  static bool scc_surplus(const SccArgs& a) { return a.prev_changed && *a.prev_changed == 0; }
+  void scc_trim(const SccArgs& a) override {
+    if (scc_surplus(a)) return;
+    auto has = [&](const ShardView& g, int64_t r, vid_t v) {
+      for (eid_t e = g.row_off[r]; e < g.row_off[r + 1]; ++e)
+        if (scc_counts(a, v, g.col[e])) return true;
+      return false;
+    };
+    for (int64_t r = 0; r < a.out.rows; ++r) {
+      const vid_t v = static_cast<vid_t>(a.out.lo + r);
+      if (a.scc[v] != kSccNone || (has(a.out, r, v) && has(a.in, r, v))) continue;
+      a.scc[v] = v;
+      ++*a.changed;
+    }
+  }
+  void scc_pivot(const SccArgs& a) override {
+    unsigned long long prod = 0;
+    vid_t id = kSccNone;
+    for (int64_t r = 0; r < a.out.rows; ++r) {
+      const vid_t v = static_cast<vid_t>(a.out.lo + r);
+      if (a.scc[v] != kSccNone) continue;
+      const unsigned long long p = static_cast<unsigned long long>(a.out.row_off[r + 1] - a.out.row_off[r]) *
+                                   static_cast<unsigned long long>(a.in.row_off[r + 1] - a.in.row_off[r]);
+      if (id == kSccNone || p > prod) prod = p, id = v;  // (ascending: ties keep the smaller)
+    }
+    a.pivot_out[0] = prod;
+    a.pivot_out[1] = id;
+  }
+  void scc_colour_init(const SccArgs& a) override {
+    for (int64_t v = 0; v < a.out.n; ++v)
+      if (a.scc[v] == kSccNone)
+        a.colour[v] = !a.pivot_only || static_cast<vid_t>(v) == a.pivot ? static_cast<vid_t>(v) : kSccNone;
+  }
+  void scc_forward(const SccArgs& a) override {
+    if (scc_surplus(a)) return;
+    for (int64_t r = 0; r < a.in.rows; ++r) {
+      const vid_t v = static_cast<vid_t>(a.in.lo + r);
+      if (a.scc[v] != kSccNone) continue;
+      vid_t m = a.colour[v];
+      // (pivot_only: the one colour there is -- a coloured v is done, the walk ends at the first hit)
+      // (... and, the first round, a neighbour with the pivot's colour counts: no class or liveness test)
+      for (eid_t e = a.in.row_off[r]; e < a.in.row_off[r + 1] && !(a.pivot_only && m != kSccNone); ++e)
+        if (a.pivot_only ? a.colour[a.in.col[e]] == a.pivot : scc_counts(a, v, a.in.col[e]))
+          m = std::min(m, a.colour[a.in.col[e]]);
+      if (m < a.colour[v]) {
+        a.colour[v] = m;
+        ++*a.changed;
+      }
+    }
+  }
+  void scc_backward(const SccArgs& a) override {
+    if (scc_surplus(a)) return;
+    for (int64_t r = 0; r < a.out.rows; ++r) {
+      const vid_t v = static_cast<vid_t>(a.out.lo + r);
+      const vid_t c = a.colour[v];
+      if (a.scc[v] != kSccNone || c == kSccNone) continue;
+      bool join = c == v;
+      for (eid_t e = a.out.row_off[r]; e < a.out.row_off[r + 1] && !join; ++e) join = a.scc[a.out.col[e]] == c;
+      if (join) {
+        a.scc[v] = c;
+        ++*a.changed;
+      }
+    }
+  }
+  void scc_end_round(const SccArgs& a) override {
+    for (int64_t v = 0; v < a.out.n; ++v)
+      if (a.scc[v] == kSccNone && a.colour[v] != kSccNone) a.cls[v] = a.colour[v];
+  }
+  void scc_relabel(const SccArgs& a) override {
+    vid_t to = kSccNone;
+    for (int64_t v = 0; v < a.out.n; ++v) {
+      if (a.scc[v] != a.pivot) continue;
+      if (to == kSccNone) to = static_cast<vid_t>(v);  // (ascending: the first member is the smallest)
+      a.scc[v] = to;
+    }
+  }
   void ms_bc_forward(const MsBcArgs& a) override {
     bc_value_type(a, [&](auto val) {
       using V = decltype(val);

@@ -260,6 +260,14 @@ class HipBackend final : public Backend {
   void cc_compress(const CcArgs& a) override { on(); kern::cc_compress(a, st_); chk(); }
   void cc_sample(const CcArgs& a) override { on(); kern::cc_sample(a, st_); chk(); }
   void cc_sizes(const CcArgs& a) override { on(); kern::cc_sizes(a, st_); chk(); }
+  void scc_init(const SccArgs& a) override { on(); kern::scc_init(a, st_); chk(); }
+  void scc_trim(const SccArgs& a) override { on(); kern::scc_trim(a, st_); chk(); }
+  void scc_pivot(const SccArgs& a) override { on(); kern::scc_pivot(a, st_); chk(); }
+  void scc_colour_init(const SccArgs& a) override { on(); kern::scc_colour_init(a, st_); chk(); }
+  void scc_forward(const SccArgs& a) override { on(); kern::scc_forward(a, st_); chk(); }
+  void scc_backward(const SccArgs& a) override { on(); kern::scc_backward(a, st_); chk(); }
+  void scc_end_round(const SccArgs& a) override { on(); kern::scc_end_round(a, st_); chk(); }
+  void scc_relabel(const SccArgs& a) override { on(); kern::scc_relabel(a, st_); chk(); }
   void widen_levels(const uint8_t* in, lvl_t* out, int64_t n, uint8_t base) override {
     on();
     kern::widen_levels(in, out, n, base, st_);

@@ -76,6 +76,10 @@ struct Args {
   bool components = false;            // --components: connected components before the traversals (Engine::components)
   std::string components_out;         // ... the labels, one per line
   int64_t cc_sample_entries = -1;     // --cc-sample-entries N (EngineOptions::cc_sample_entries; -1: the default)
+  bool strong_components = false;     // --strong-components: strongly connected components before the traversals
+  std::string strong_components_out;  // ... the labels, one per line
+  int64_t scc_trim_rounds = -2;       // --scc-trim-rounds N (EngineOptions::scc_trim_rounds; -2: the default)
+  bool scc_pivot = true;              // --no-scc-pivot clears it (EngineOptions::scc_pivot)
   bool mode_given = false;            // --mode on the command line (--directed turns only the default into td)
   std::vector<std::pair<std::string, double>> opts;  // --opt name=value, in order (set_engine_option)
 };
@@ -98,6 +102,12 @@ struct Args {
                "       --components [--components-out FILE] (connected components on the device before the traversals: count,\n"
                "                   largest, singletons; the labels checked against the sequential oracle unless --no-oracle)\n"
                "       --cc-sample-entries N (entries per row hooked before the largest component is skipped; 0: one full pass)\n"
+               "       --strong-components [--strong-components-out FILE] (strongly connected components on the device\n"
+               "                   before the traversals, after --components: count, largest, singletons, trimmed, rounds;\n"
+               "                   the labels checked against the sequential Tarjan oracle unless --no-oracle; an undirected\n"
+               "                   graph: its connected components)\n"
+               "       --scc-trim-rounds N (trim sweeps per round at most; -1: to the fixed point, the default; 0: no trim)\n"
+               "       --no-scc-pivot (colour every vertex in the first round instead of one high-degree pivot)\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only; --batch and --validate work on the in-edge shard,\n"
@@ -153,6 +163,10 @@ Args parse(int argc, char** argv) {
     else if (s == "--components") a.components = true;
     else if (s == "--components-out") a.components_out = next();
     else if (s == "--cc-sample-entries") a.cc_sample_entries = std::stoll(next());
+    else if (s == "--strong-components") a.strong_components = true;
+    else if (s == "--strong-components-out") a.strong_components_out = next();
+    else if (s == "--scc-trim-rounds") a.scc_trim_rounds = std::stoll(next());
+    else if (s == "--no-scc-pivot") a.scc_pivot = false;
     else if (s == "--no-oracle") a.oracle = false;
     else if (s == "--validate") a.validate = true;
     else if (s == "--levels-out") a.levels_out = next();
@@ -208,6 +222,9 @@ Args parse(int argc, char** argv) {
   }
   if (!a.components_out.empty() && !a.components) usage("--components-out needs --components");
   if (a.cc_sample_entries < -1) usage("--cc-sample-entries must be >= 0");
+  if (!a.strong_components_out.empty() && !a.strong_components)
+    usage("--strong-components-out needs --strong-components");
+  if (a.scc_trim_rounds < -2) usage("--scc-trim-rounds must be >= -1");
   if (a.directed) {
     // a single-source traversal is top-down only (the bottom-up kernels take
     // their degrees from their own rows); --batch pulls over the in-edge shard
@@ -573,6 +590,8 @@ int main(int argc, char** argv) {
     eo.phase_timing = a.phase_timing;
     eo.directed = a.directed;
     if (a.cc_sample_entries >= 0) eo.cc_sample_entries = a.cc_sample_entries;
+    if (a.scc_trim_rounds >= -1) eo.scc_trim_rounds = a.scc_trim_rounds;
+    if (!a.scc_pivot) eo.scc_pivot = false;
     for (const auto& kv : a.opts) set_engine_option(eo, kv.first, kv.second);
     run_ranks(ranks, [&](int i, RankCtx& rc) {
       const int rk = multiproc ? wrank : i;
@@ -643,6 +662,51 @@ int main(int argc, char** argv) {
                       gname.c_str(), static_cast<long long>(n), P, static_cast<long long>(c.components),
                       static_cast<long long>(c.largest_label), static_cast<long long>(c.largest_size),
                       static_cast<long long>(c.singletons), c.ms, c.link_ms, c.compress_ms, c.sampled ? "true" : "false");
+      }
+    }
+
+    // ---- strongly connected components (--strong-components), before the traversals ----
+    if (a.strong_components) {
+      std::vector<SccResult> sres(static_cast<size_t>(nlocal));
+      std::vector<int64_t> labels;
+      run_ranks(ranks, [&](int i, RankCtx& rc) {
+        sres[i] = rc.engine->strong_components();
+        if (i == 0 && leader && ((a.oracle && have_host) || !a.strong_components_out.empty()))
+          labels = rc.engine->gather_strong_components();
+      }, vgroup.get());
+      if (leader) {
+        const SccResult& c = sres[0];
+        std::printf("strong components %lld largest label %lld size %lld singletons %lld trimmed %lld rounds %lld ms %.3f\n",
+                    static_cast<long long>(c.components), static_cast<long long>(c.largest_label),
+                    static_cast<long long>(c.largest_size), static_cast<long long>(c.singletons),
+                    static_cast<long long>(c.trimmed), static_cast<long long>(c.rounds), c.ms);
+        if (a.oracle && have_host) {
+          const std::vector<int64_t> exp = cpu_strong_components(full);
+          for (int64_t i = 0; i < n; ++i) {
+            if (labels[i] != exp[i]) {
+              std::printf("strong component %lld %lld %lld\n", static_cast<long long>(i),
+                          static_cast<long long>(labels[i]), static_cast<long long>(exp[i]));
+              std::printf("Wrong output!\n");
+              return 1;
+            }
+          }
+          if (!a.quiet) std::printf("Strong components OK!\n");
+        }
+        if (!a.strong_components_out.empty()) {
+          std::FILE* f = std::fopen(a.strong_components_out.c_str(), "w");
+          DBFS_CHECK(f != nullptr, "cannot write " + a.strong_components_out);
+          for (int64_t l : labels) std::fprintf(f, "%lld\n", static_cast<long long>(l));
+          std::fclose(f);
+        }
+        if (a.json)
+          std::printf("{\"graph\":\"%s\",\"n\":%lld,\"ranks\":%d,\"strong_components\":%lld,\"largest_label\":%lld,"
+                      "\"largest_size\":%lld,\"singletons\":%lld,\"trimmed\":%lld,\"rounds\":%lld,\"ms\":%.6f,"
+                      "\"scc_trim_ms\":%.6f,\"scc_colour_ms\":%.6f,\"scc_sweeps\":%lld,\"scc_pivot\":%lld}\n",
+                      gname.c_str(), static_cast<long long>(n), P, static_cast<long long>(c.components),
+                      static_cast<long long>(c.largest_label), static_cast<long long>(c.largest_size),
+                      static_cast<long long>(c.singletons), static_cast<long long>(c.trimmed),
+                      static_cast<long long>(c.rounds), c.ms, c.trim_ms, c.colour_ms, static_cast<long long>(c.sweeps),
+                      static_cast<long long>(c.pivot));
       }
     }
 

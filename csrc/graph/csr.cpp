@@ -105,6 +105,59 @@ std::vector<int64_t> cpu_components(const HostCSR& g) {
   return label;
 }
 
+// Tarjan's algorithm with the recursion as an explicit stack of (vertex, next
+// entry) frames; a component is popped when its root's frame ends, and gets
+// the smallest id among the popped.  Shares nothing with the backends' sweeps.
+std::vector<int64_t> cpu_strong_components(const HostCSR& g) {
+  DBFS_CHECK(g.row_lo == 0 && g.rows == g.n, "cpu_strong_components expects a full CSR");
+  const size_t n = static_cast<size_t>(g.n);
+  constexpr int64_t kUnseen = -1;
+  std::vector<int64_t> index(n, kUnseen), low(n, 0), label(n, kUnseen);
+  std::vector<char> on_stack(n, 0);
+  std::vector<int64_t> stack;
+  std::vector<std::pair<int64_t, eid_t>> frames;
+  int64_t next_index = 0;
+  for (int64_t s = 0; s < g.n; ++s) {
+    if (index[s] != kUnseen) continue;
+    frames.emplace_back(s, g.row_off[s]);
+    index[s] = low[s] = next_index++;
+    stack.push_back(s);
+    on_stack[s] = 1;
+    while (!frames.empty()) {
+      const int64_t v = frames.back().first;
+      eid_t& e = frames.back().second;
+      if (e < g.row_off[v + 1]) {
+        const int64_t w = g.col[e++];
+        if (index[w] == kUnseen) {
+          index[w] = low[w] = next_index++;
+          stack.push_back(w);
+          on_stack[w] = 1;
+          frames.emplace_back(w, g.row_off[w]);  // (invalidates e: the loop re-reads the frame)
+        } else if (on_stack[w]) {
+          low[v] = std::min(low[v], index[w]);
+        }
+        continue;
+      }
+      frames.pop_back();
+      if (!frames.empty()) low[frames.back().first] = std::min(low[frames.back().first], low[v]);
+      if (low[v] != index[v]) continue;
+      // v is its component's root: the stack from v up is the component
+      size_t first = stack.size();
+      int64_t smallest = v;
+      do {
+        --first;
+        smallest = std::min(smallest, stack[first]);
+      } while (stack[first] != v);
+      for (size_t i = first; i < stack.size(); ++i) {
+        label[stack[i]] = smallest;
+        on_stack[stack[i]] = 0;
+      }
+      stack.resize(first);
+    }
+  }
+  return label;
+}
+
 namespace {
 
 // cpu_betweenness' two count forms: a count, how it is added, tested, kept,

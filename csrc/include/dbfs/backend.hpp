@@ -32,11 +32,11 @@ enum class DeviceKind { CPU, HIP };
 // Device-checked build: the kernel files that record bounds violations, each
 // in a word of its own (the codes of two files may coincide: a violation is
 // reported with its file).
-enum class CheckFile { Bfs, Td, Bu, Ms, MsBc, Cc, Graph };
-constexpr int kCheckFiles = 7;
+enum class CheckFile { Bfs, Td, Bu, Ms, MsBc, Cc, Graph, Scc };
+constexpr int kCheckFiles = 8;
 inline const char* check_file_name(CheckFile f) {
   constexpr const char* names[kCheckFiles] = {"bfs_kernels", "td_kernels",  "bu_kernels",   "ms_kernels",
-                                              "ms_bc_kernels", "cc_kernels", "graph_kernels"};
+                                              "ms_bc_kernels", "cc_kernels", "graph_kernels", "scc_kernels"};
   return names[static_cast<int>(f)];
 }
 
@@ -1329,6 +1329,58 @@ struct CcArgs {
   int64_t* slots = nullptr;        // HIP: kCcSizeGrid x kCcTotals
 };
 
+// Strongly connected components (Engine::strong_components): trim, forward
+// colouring and backward closure over the out- and in-rows.  Every array has
+// one entry per vertex of the whole graph (several ranks: every rank its own
+// replica; a sweep writes only the entries of its owned rows, the engine
+// all-gathers them).  scc[v] == kSccNone while v is live; an edge u -> w counts
+// when u != w, both ends are live and cls[u] == cls[w].
+//   scc_init         scc = cls = colour = kSccNone for every v < n.
+//   scc_trim         one sweep over the owned rows: a live v with no counting
+//     out-edge or no counting in-edge gets scc[v] = v; *changed += settled.
+//   scc_pivot        pivot_out[0..1] = (in-degree x out-degree, id) of the live
+//     owned vertex with the largest product (stored entries, duplicates and
+//     self-loops included), the smaller id on a tie; id kSccNone when none.
+//   scc_colour_init  live v (all n): colour[v] = v, or with pivot_only: v for
+//     v == pivot and kSccNone otherwise.
+//   scc_forward      one pull sweep over the owned in-rows: colour[v] = min(
+//     colour[v], colour[u]) over counting in-neighbours u; *changed += changes.
+//     With pivot_only the only colour is the pivot's: an uncoloured v takes it
+//     from the first in-neighbour that has it, a coloured v is done.  (First
+//     round only: all classes are equal and no colour of an earlier round is
+//     left, so an in-neighbour with the pivot's colour counts.)
+//   scc_backward     one pull sweep over the owned out-rows: a live v with
+//     colour c joins (scc[v] = c) when v == c or some out-neighbour w has
+//     scc[w] == c; *changed += joined.  (No other SCC ever has the label of a
+//     live root, so scc[w] == c alone says "w has this colour and is in".)
+//   scc_end_round    live v (all n) with a colour: cls[v] = colour[v].
+//   scc_relabel      (all n) every v with scc[v] == pivot gets the smallest
+//     such v (the pivot round's label is the pivot, not the minimum).
+// Values only fall (colour) or settle once (scc), and each sweep's fixed point
+// is unique: a sweep may read entries other rows stored during the same
+// launch, in any order.  out.col / in.col hold plain vertex ids.
+constexpr vid_t kSccNone = 0xFFFFFFFFu;
+// HIP, scc_pivot: workgroups at most, each with a slot of two words.
+constexpr int kSccPivotGrid = 1024;
+struct SccArgs {
+  ShardView out, in;               // the owned rows of the adjacency and of the in-edge shard (same lo, rows, n)
+  vid_t* scc = nullptr;            // n entries each
+  vid_t* cls = nullptr;
+  vid_t* colour = nullptr;
+  unsigned long long* changed = nullptr;  // this sweep's counter (the engine zeroes it)
+  // The counter of the sweep enqueued before this one, of the same step
+  // (nullptr: none): when it is zero that sweep was at the fixed point, and
+  // this one returns at once -- a surplus sweep costs its launch only.
+  const unsigned long long* prev_changed = nullptr;
+  // scc_pivot
+  unsigned long long* pivot_out = nullptr;    // 2 words
+  unsigned long long* pivot_slots = nullptr;  // HIP: kSccPivotGrid x 2
+  // scc_colour_init / scc_relabel
+  vid_t pivot = kSccNone;
+  bool pivot_only = false;
+  vid_t* relabel_min = nullptr;    // HIP: one word
+};
+
 // ---- backend ----------------------------------------------------------------
 
 class Backend {
@@ -1560,6 +1612,15 @@ class Backend {
   virtual void cc_compress(const CcArgs& a) = 0;
   virtual void cc_sample(const CcArgs& a) = 0;
   virtual void cc_sizes(const CcArgs& a) = 0;
+  // strongly connected components (SccArgs)
+  virtual void scc_init(const SccArgs& a) = 0;
+  virtual void scc_trim(const SccArgs& a) = 0;
+  virtual void scc_pivot(const SccArgs& a) = 0;
+  virtual void scc_colour_init(const SccArgs& a) = 0;
+  virtual void scc_forward(const SccArgs& a) = 0;
+  virtual void scc_backward(const SccArgs& a) = 0;
+  virtual void scc_end_round(const SccArgs& a) = 0;
+  virtual void scc_relabel(const SccArgs& a) = 0;
 
  protected:
   std::function<void(double)> wait_watch_;

@@ -402,6 +402,11 @@ struct EngineOptions {
   // sorted, so the first entries are the hubs).  0: one pass over every entry,
   // which directed graphs and several ranks always run.
   int64_t cc_sample_entries = 2;
+  // strong_components(): trim sweeps per round at most (-1: to the fixed
+  // point; 0: no trim), and whether the first round colours only a pivot (the
+  // live vertex with the largest in-degree x out-degree) instead of every vertex.
+  int64_t scc_trim_rounds = -1;
+  bool scc_pivot = true;
 };
 
 // Named access to the numeric tuning options (alpha, beta, bu_lane_limit,
@@ -550,6 +555,28 @@ struct ComponentsResult {
   bool sampled = false;        // the sample-and-skip form ran
 };
 
+// Engine::strong_components.  trim_rounds < -1 / pivot < 0: the engine options
+// scc_trim_rounds / scc_pivot.
+struct SccOptions {
+  int64_t trim_rounds = -2;
+  int pivot = -1;
+};
+
+struct SccResult {
+  int64_t components = 0;      // strongly connected components
+  int64_t largest_label = -1;  // the largest one's label (its smallest vertex; the smaller label on a tie)
+  int64_t largest_size = 0;
+  int64_t singletons = 0;      // components of one vertex
+  int64_t trimmed = 0;         // vertices the trim settled (<= singletons)
+  int64_t rounds = 0;          // colouring rounds (<= n)
+  int64_t sweeps = 0;          // sweep launches of all three steps
+  int64_t pivot = -1;          // the first round's pivot (-1: none)
+  int64_t pivot_size = 0;      // ... and the size of its component
+  double ms = 0.0;             // wall time, max over ranks
+  double trim_ms = 0.0;        // the trim sweeps
+  double colour_ms = 0.0;      // the colouring rounds (forward and backward sweeps)
+};
+
 // Fault injection for failure-detection tests (see Engine::inject_fault).
 struct FaultSpec {
   int rank = -1, level = -1;
@@ -663,6 +690,27 @@ class Engine {
   std::vector<int64_t> gather_component_sizes();
   bool has_components() const { return cc_ && cc_->valid; }
   const ComponentsResult& last_components() const;
+  // Strongly connected components of the whole graph on the device;
+  // collective.  label[v] = the smallest vertex id of v's strongly connected
+  // component (an undirected graph: its connected components).  Rounds of
+  // trim, forward colouring over the in-edge rows and backward closure over
+  // the out-rows (Backend::scc_*; csrc/engine/strong_components.cpp), every
+  // "until nothing changes" loop on the host over a device counter, no
+  // traversal per component.  A directed graph's in-edge shard is built by the
+  // first call if it is not there.  Several ranks, the simple form: every rank
+  // holds the state of all n vertices, a sweep writes its owned rows' entries
+  // and the owned slices are all-gathered after every sweep -- correct, not
+  // fast.  Device state: 12 B per vertex of the whole graph (label, class,
+  // colour) and 4 B for the sizes, allocated by the first call and kept; apart
+  // from run / run_batch / validate / components state.
+  SccResult strong_components(const SccOptions& o = {});
+  // The last strong_components() call's labels, and every vertex's component
+  // size, for all n vertices (this rank's replica: no communication).  Throw
+  // when strong_components() has not run.
+  std::vector<int64_t> gather_strong_components();
+  std::vector<int64_t> gather_strong_component_sizes();
+  bool has_strong_components() const { return scc_ && scc_->valid; }
+  const SccResult& last_strong_components() const;
   // Test hook: overwrite source slot `slot`'s level of global `vertex` in the
   // resident level matrix (on its owner; level < 0: unreached), so a test can
   // plant a violation for validate_batch_pass to find.
@@ -830,6 +878,19 @@ class Engine {
     ComponentsResult last;
   };
   std::unique_ptr<CcBuffers> cc_;
+  // strong-components state (csrc/engine/strong_components.cpp), allocated by
+  // the first strong_components() call; separate from everything above
+  struct SccBuffers {
+    DBuf<vid_t> scc, cls, colour;  // SccArgs: nranks x part entries (an owned slice is all-gathered whole)
+    DBuf<vid_t> xchg;              // several ranks: the all-gather's receive buffer
+    DBuf<uint32_t> size;           // CcArgs::size (cc_sizes over the labels)
+    DBuf<unsigned long long> words;  // changed, pivot_out[2], relabel_min
+    DBuf<unsigned long long> pivot_slots, pivot_all;
+    DBuf<int64_t> totals, slots;   // CcArgs::totals / slots
+    bool valid = false;            // scc and size hold the last call's result
+    SccResult last;
+  };
+  std::unique_ptr<SccBuffers> scc_;
   // 0: done; 1: deeper than the level type holds (rerun wider)
   int run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out);
   void collect_batch_levels();

@@ -97,6 +97,13 @@ CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src);
 // nothing; a vertex without entries is its own component.
 std::vector<int64_t> cpu_components(const HostCSR& g);
 
+// Sequential strongly-connected-components oracle (Tarjan 1972, an explicit
+// stack instead of the recursion): label[v] = the smallest vertex id of v's
+// strongly connected component over the stored entries u -> w.  Self-loops
+// and duplicates change nothing; an undirected CSR (every edge stored in both
+// rows) gives cpu_components' labels.
+std::vector<int64_t> cpu_strong_components(const HostCSR& g);
+
 // Sequential betweenness oracle (Brandes 2001: a queue, the visit order as a
 // stack, a predecessor scan), one source at a time.  Entries are the stored
 // adjacency entries, duplicates and self-loops kept: sigma_s(s) = 1, and for a

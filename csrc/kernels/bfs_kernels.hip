@@ -771,19 +771,22 @@ void inject_check_failure(CheckFile f, hipStream_t st) {
     case CheckFile::MsBc: inject_check_ms_bc(st); break;
     case CheckFile::Cc: inject_check_cc(st); break;
     case CheckFile::Graph: inject_check_graph(st); break;
+    case CheckFile::Scc: inject_check_scc(st); break;
   }
 }
 
 // Every kernel file that records violations compiled its check sites (a
 // checked build that leaves one out is not a checked build).
 bool checks_enabled() {
-  return kCheckedLocal && kCheckedTd && kCheckedBu && kCheckedMs && kCheckedMsBc && kCheckedCc && kCheckedGraph;
+  return kCheckedLocal && kCheckedTd && kCheckedBu && kCheckedMs && kCheckedMsBc && kCheckedCc && kCheckedGraph &&
+         kCheckedScc;
 }
 
 unsigned long long take_check_error(CheckFile* file) {
   // (each kernel file records into its own g_check; all are read and cleared)
   const unsigned long long h[kCheckFiles] = {take_check_local(), take_check_td(), take_check_bu(), take_check_ms(),
-                                             take_check_ms_bc(), take_check_cc(), take_check_graph()};
+                                             take_check_ms_bc(), take_check_cc(), take_check_graph(),
+                                             take_check_scc()};
   for (int i = 0; i < kCheckFiles; ++i)
     if (h[i]) {
       if (file) *file = static_cast<CheckFile>(i);

@@ -84,6 +84,16 @@ void cc_compress(const CcArgs& a, hipStream_t st);
 void cc_sample(const CcArgs& a, hipStream_t st);
 void cc_sizes(const CcArgs& a, hipStream_t st);
 
+// scc_kernels.hip (strongly connected components: SccArgs)
+void scc_init(const SccArgs& a, hipStream_t st);
+void scc_trim(const SccArgs& a, hipStream_t st);
+void scc_pivot(const SccArgs& a, hipStream_t st);
+void scc_colour_init(const SccArgs& a, hipStream_t st);
+void scc_forward(const SccArgs& a, hipStream_t st);
+void scc_backward(const SccArgs& a, hipStream_t st);
+void scc_end_round(const SccArgs& a, hipStream_t st);
+void scc_relabel(const SccArgs& a, hipStream_t st);
+
 // peer_kernels.hip (PeerComm: collectives through peer-mapped windows)
 constexpr int kMaxPeers = 16;
 struct PeerPushArgs {

@@ -243,6 +243,19 @@ PYBIND11_MODULE(_dbfs_native, m) {
       },
       py::arg("csr"));
 
+  // sequential strongly-connected-components oracle: int64 [n], the smallest id of every vertex's SCC
+  m.def(
+      "cpu_strong_components",
+      [](const HostCSR& g) {
+        std::vector<int64_t> r;
+        {
+          py::gil_scoped_release rel;
+          r = cpu_strong_components(g);
+        }
+        return to_numpy(r);
+      },
+      py::arg("csr"));
+
   py::class_<GenParams>(m, "GenParams")
       .def_readonly("n", &GenParams::n)
       .def_readonly("m", &GenParams::m)
@@ -781,6 +794,20 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def_readonly("compress_ms", &ComponentsResult::compress_ms)
       .def_readonly("sampled", &ComponentsResult::sampled);
 
+  py::class_<SccResult>(m, "StrongComponentsResult")
+      .def_readonly("components", &SccResult::components)
+      .def_readonly("largest_label", &SccResult::largest_label)
+      .def_readonly("largest_size", &SccResult::largest_size)
+      .def_readonly("singletons", &SccResult::singletons)
+      .def_readonly("trimmed", &SccResult::trimmed)
+      .def_readonly("rounds", &SccResult::rounds)
+      .def_readonly("sweeps", &SccResult::sweeps)
+      .def_readonly("pivot", &SccResult::pivot)
+      .def_readonly("pivot_size", &SccResult::pivot_size)
+      .def_readonly("ms", &SccResult::ms)
+      .def_readonly("trim_ms", &SccResult::trim_ms)
+      .def_readonly("colour_ms", &SccResult::colour_ms);
+
   py::class_<Engine, std::shared_ptr<Engine>>(m, "Engine")
       .def(py::init([](std::shared_ptr<DeviceGraph> g, std::shared_ptr<Comm> c, const std::string& mode, double alpha,
                        double beta, int bu_lane_limit, bool phase_timing, bool force_exchange) {
@@ -915,6 +942,38 @@ PYBIND11_MODULE(_dbfs_native, m) {
              {
                py::gil_scoped_release rel;
                v = e.gather_component_sizes();
+             }
+             return to_numpy(v);
+           })
+      // strongly connected components (trim_rounds < -1 / pivot < 0: the engine options)
+      .def(
+          "strong_components",
+          [](Engine& e, int64_t trim_rounds, int pivot) {
+            SccOptions o;
+            o.trim_rounds = trim_rounds;
+            o.pivot = pivot;
+            py::gil_scoped_release rel;
+            return e.strong_components(o);
+          },
+          py::arg("trim_rounds") = -2, py::arg("pivot") = -1)
+      .def_property_readonly("has_strong_components", &Engine::has_strong_components)
+      .def("last_strong_components", [](const Engine& e) { return e.last_strong_components(); })
+      // the last strong_components() call's labels / per-vertex component sizes: int64 [n]
+      .def("gather_strong_components",
+           [](Engine& e) {
+             std::vector<int64_t> v;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_strong_components();
+             }
+             return to_numpy(v);
+           })
+      .def("gather_strong_component_sizes",
+           [](Engine& e) {
+             std::vector<int64_t> v;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_strong_component_sizes();
              }
              return to_numpy(v);
            })

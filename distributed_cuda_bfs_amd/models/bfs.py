@@ -140,6 +140,31 @@ class ComponentsResult:
                 f"sampled={self.sampled})")
 
 
+class StrongComponentsResult:
+    """Strongly connected components of the whole graph
+    (``BFS.strong_components``): ``components`` (how many), ``largest_label``
+    / ``largest_size`` (the largest one: its smallest vertex id and its vertex
+    count; the smaller label on a tie), ``singletons`` (components of one
+    vertex), ``trimmed`` (vertices the trim settled), ``rounds`` (rounds of
+    trim, colouring and closure), ``sweeps`` (sweep launches of all steps),
+    ``pivot`` / ``pivot_size`` (the first round's pivot vertex, -1 when none,
+    and the size of its component), ``ms`` (wall time, max over ranks) with
+    its ``trim_ms`` and ``colour_ms`` parts."""
+
+    __slots__ = ("components", "largest_label", "largest_size", "singletons", "trimmed", "rounds", "sweeps", "pivot",
+                 "pivot_size", "ms", "trim_ms", "colour_ms")
+
+    def __init__(self, r: Any):
+        for name in self.__slots__[:9]:
+            setattr(self, name, int(getattr(r, name)))
+        self.ms, self.trim_ms, self.colour_ms = float(r.ms), float(r.trim_ms), float(r.colour_ms)
+
+    def __repr__(self) -> str:
+        return (f"StrongComponentsResult(components={self.components}, largest_label={self.largest_label}, "
+                f"largest_size={self.largest_size}, singletons={self.singletons}, trimmed={self.trimmed}, "
+                f"rounds={self.rounds}, sweeps={self.sweeps}, pivot={self.pivot}, ms={self.ms:.4f})")
+
+
 class BFS:
     """Distributed BFS over a graph given as a HostCSR, generator params, or a file path."""
 
@@ -392,16 +417,50 @@ class BFS:
         """int64 [n]: entry v is the number of vertices in v's component (last components())."""
         return self.engine.gather_component_sizes()
 
-    def _component_roots(self, k: int, seed: int, component) -> List[int]:
-        if not self.engine.has_components:
+    def strong_components(self, trim_rounds: Optional[int] = None, pivot: Optional[bool] = None) -> StrongComponentsResult:
+        """Strongly connected components of the whole graph on the device
+        (collective): label[v] = the smallest vertex id of v's strongly
+        connected component; on an undirected graph the connected components.
+        Rounds of trim (a vertex without a live in- or out-neighbour of its
+        class is its own component), forward colouring (the smallest id that
+        reaches each vertex, pulled over the in-edges) and backward closure
+        (the vertices of a colour that reach its root), each swept until
+        nothing changes; no traversal per component.  ``trim_rounds`` (default:
+        the engine option ``scc_trim_rounds``, -1): trim sweeps per round at
+        most, -1 to the fixed point, 0 none.  ``pivot`` (default: the engine
+        option ``scc_pivot``, on): the first round colours only the live vertex
+        with the largest in-degree x out-degree, which settles a giant
+        component in two reaches.  The labels are the same whatever the
+        options.  A directed graph's in-edge shard is built by the first call.
+        Several ranks all-gather the state after every sweep: correct, not
+        fast.  16 bytes per vertex of the whole graph on the device, kept; the
+        state of run / run_batch / validate / components is left alone."""
+        return StrongComponentsResult(self.engine.strong_components(
+            -2 if trim_rounds is None else int(trim_rounds), -1 if pivot is None else int(bool(pivot))))
+
+    def strong_component_labels(self) -> np.ndarray:
+        """Labels of the last strong_components() as int64 [n]."""
+        return self.engine.gather_strong_components()
+
+    def strong_component_sizes(self) -> np.ndarray:
+        """int64 [n]: entry v is the number of vertices in v's strongly connected component (last strong_components())."""
+        return self.engine.gather_strong_component_sizes()
+
+    def _component_roots(self, k: int, seed: int, component, strong: bool = False) -> List[int]:
+        what = "strong_component" if strong else "component"
+        if strong and not self.engine.has_strong_components:
+            self.strong_components()
+        if not strong and not self.engine.has_components:
             self.components()
         if isinstance(component, str):
             if component != "largest":
-                raise ValueError('component must be None, "largest" or a component label')
-            label = int(self.engine.last_components().largest_label)
+                raise ValueError(f'{what} must be None, "largest" or a component label')
+            last = self.engine.last_strong_components() if strong else self.engine.last_components()
+            label = int(last.largest_label)
         else:
             label = int(component)
-        members = np.nonzero(self.component_labels() == label)[0]
+        labels = self.strong_component_labels() if strong else self.component_labels()
+        members = np.nonzero(labels == label)[0]
         roots: List[int] = []
         if members.size >= k:
             for v in np.random.default_rng(seed).permutation(members):
@@ -410,15 +469,21 @@ class BFS:
                 if self.degree(int(v)) > 0:
                     roots.append(int(v))
         if len(roots) < k:
-            raise ValueError(f"component {label} has fewer than {k} vertices of degree >= 1")
+            raise ValueError(f"{what.replace('_', ' ')} {label} has fewer than {k} vertices of degree >= 1")
         return roots
 
-    def sample_roots(self, k: int, seed: int = 1, component=None) -> List[int]:
+    def sample_roots(self, k: int, seed: int = 1, component=None, strong_component=None) -> List[int]:
         """Graph500 root sampling: k distinct random vertices of degree >= 1 (collective).
         ``component="largest"`` samples them from the largest connected
         component (running components() first if it has not run), an int from
         the component with that label; raises ValueError when the component
-        has fewer than k vertices of degree >= 1."""
+        has fewer than k vertices of degree >= 1.  ``strong_component`` does
+        the same over the strongly connected components (strong_components());
+        giving both is a ValueError."""
+        if component is not None and strong_component is not None:
+            raise ValueError("sample_roots takes component or strong_component, not both")
+        if strong_component is not None:
+            return self._component_roots(int(k), seed, strong_component, strong=True)
         if component is not None:
             return self._component_roots(int(k), seed, component)
         rng = np.random.default_rng(seed)

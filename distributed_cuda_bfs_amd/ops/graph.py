@@ -88,6 +88,13 @@ def cpu_components(csr):
     return N.cpu_components(csr)
 
 
+def cpu_strong_components(csr):
+    """Sequential strongly-connected-components oracle (Tarjan, explicit
+    stack): int64 [n], label[v] = the smallest vertex id of v's strongly
+    connected component over the stored entries u -> w."""
+    return N.cpu_strong_components(csr)
+
+
 def cpu_betweenness(csr, sources, directed: bool = False, path_counts: bool = False, wide_counts: bool = False):
     """Sequential Brandes oracle over the stored adjacency entries (duplicates
     are parallel edges, self-loops never lie on a shortest path): returns

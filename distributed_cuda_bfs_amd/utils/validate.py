@@ -171,3 +171,47 @@ def component_labels_reference(csr) -> np.ndarray:
         if np.array_equal(new, label):
             return label
         label = new
+
+
+def strong_component_labels_reference(csr) -> np.ndarray:
+    """Strongly-connected-component labels by numpy peeling, int64[n]:
+    label[v] = the smallest vertex id of v's strongly connected component over
+    the stored entries u -> w (self-loops ignored).  Among the entries whose
+    two ends are still unlabelled: vertices without an in- or an out-entry are
+    peeled as their own components until none is left; then the smallest
+    unlabelled vertex p is taken, its forward and its backward reachability
+    closures are grown with np.minimum.at until they stop growing, and their
+    intersection is p's component, labelled p (nothing smaller is unlabelled).
+    One closure pair per component of two or more vertices, each step a pass
+    over all remaining entries: slow, for tests only; independent of
+    cpu_strong_components and of the backends."""
+    ro = np.asarray(csr.row_off)
+    n = int(csr.n)
+    w = np.asarray(csr.col).astype(np.int64)
+    u = np.repeat(np.arange(n, dtype=np.int64), np.diff(ro))
+    keep = u != w
+    u, w = u[keep], w[keep]
+    label = np.full(n, -1, dtype=np.int64)
+
+    def closure(start, src, dst):
+        far = np.ones(n, dtype=np.int64)  # 0: reached
+        far[start] = 0
+        while True:
+            before = int(far.sum())
+            np.minimum.at(far, dst, far[src])
+            if int(far.sum()) == before:
+                return far == 0
+
+    while True:
+        while True:
+            live = (label[u] < 0) & (label[w] < 0)
+            u, w = u[live], w[live]
+            alone = (label < 0) & ((np.bincount(u, minlength=n) == 0) | (np.bincount(w, minlength=n) == 0))
+            if not alone.any():
+                break
+            label[alone] = np.nonzero(alone)[0]
+        rest = np.nonzero(label < 0)[0]
+        if rest.size == 0:
+            return label
+        p = int(rest[0])
+        label[closure(p, u, w) & closure(p, w, u)] = p
