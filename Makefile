@@ -23,9 +23,9 @@ LDLIBS    := -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -Wl,-rpath,
 
 HOST_SRC  := csrc/graph/io.cpp csrc/graph/csr.cpp csrc/backend/cpu_backend.cpp \
              csrc/backend/hip_backend.cpp csrc/comm/comm.cpp csrc/comm/nccl_comm.cpp \
-             csrc/comm/tcp_bootstrap.cpp csrc/comm/peer_comm.cpp csrc/comm/replay_comm.cpp csrc/engine/engine.cpp csrc/engine/batch.cpp csrc/engine/device_loop.cpp csrc/engine/components.cpp csrc/engine/strong_components.cpp csrc/graph/shard_reader.cpp
+             csrc/comm/tcp_bootstrap.cpp csrc/comm/peer_comm.cpp csrc/comm/replay_comm.cpp csrc/engine/engine.cpp csrc/engine/batch.cpp csrc/engine/device_loop.cpp csrc/engine/components.cpp csrc/engine/strong_components.cpp csrc/engine/eccentricity.cpp csrc/graph/shard_reader.cpp
 HIP_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/graph_kernels.hip csrc/kernels/ref_kernels.hip \
-             csrc/kernels/graph_sort.hip csrc/kernels/peer_kernels.hip csrc/kernels/ms_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip csrc/kernels/scc_kernels.hip
+             csrc/kernels/graph_sort.hip csrc/kernels/peer_kernels.hip csrc/kernels/ms_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip csrc/kernels/scc_kernels.hip csrc/kernels/ecc_kernels.hip
 
 HOST_OBJ  := $(patsubst csrc/%.cpp,$(BUILD)/%.o,$(HOST_SRC))
 HIP_OBJ   := $(patsubst csrc/%.hip,$(BUILD)/%.o,$(HIP_SRC))
@@ -41,7 +41,7 @@ lib: $(CORE_LIB)
 
 # Device-checked build: bin/bfs_checked, every kernel file with
 # DBFS_DCHECK sites built with -DDBFS_CHECKED: the traversal, batch,
-# betweenness, components, strong-components and graph-build (in-edge routing) kernels verify
+# betweenness, components, strong-components, eccentricity and graph-build (in-edge routing) kernels verify
 # the bounds of their work lists, owner lists, rows and vertex ids on the
 # device; the first violation fails the run on the host, named with its file
 # (HipBackend::take_device_check).  CHECKED_SRC lists every such file (one
@@ -49,7 +49,7 @@ lib: $(CORE_LIB)
 # +checked only when all of them compiled their sites.  Host code and the
 # kernel files without sites (ref_kernels, graph_sort, peer_kernels) unchanged.
 CHECKED_BUILD := build-checked
-CHECKED_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/ms_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip csrc/kernels/graph_kernels.hip csrc/kernels/scc_kernels.hip
+CHECKED_SRC   := csrc/kernels/bfs_kernels.hip csrc/kernels/td_kernels.hip csrc/kernels/bu_kernels.hip csrc/kernels/ms_kernels.hip csrc/kernels/ms_bc_kernels.hip csrc/kernels/cc_kernels.hip csrc/kernels/graph_kernels.hip csrc/kernels/scc_kernels.hip csrc/kernels/ecc_kernels.hip
 CHECKED_OBJ   := $(patsubst csrc/%.hip,$(CHECKED_BUILD)/%.o,$(CHECKED_SRC))
 checked: bin/bfs_checked
 $(CHECKED_BUILD)/%.o: csrc/%.hip $(HEADERS)

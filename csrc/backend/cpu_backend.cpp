@@ -558,6 +558,94 @@ class CpuBackend final : public Backend {
       a.scc[v] = to;
     }
   }
+  // eccentricity bounding (EccArgs): the device's stages as plain loops
+  void ecc_degrees(const EccArgs& a) override {
+    for (int64_t r = 0; r < a.g.rows; ++r) a.deg_own[r] = static_cast<uint32_t>(a.g.row_off[r + 1] - a.g.row_off[r]);
+  }
+  void ecc_init(const EccArgs& a) override {
+    for (int64_t v = 0; v < a.g.n; ++v) {
+      const bool in = a.scope_all || a.comp[v] == a.label;
+      const bool empty = a.deg[v] == 0u;
+      a.lo[v] = in ? 0 : -1;
+      a.hi[v] = in ? (empty ? 0 : INT32_MAX) : -1;
+      a.state[v] = in ? kEccScope | (empty ? kEccSettled : kEccLive) : 0u;
+    }
+  }
+  void ecc_select(const EccArgs& a) override {
+    auto key = [](uint32_t value, int64_t v) {
+      return (static_cast<uint64_t>(value) << 32) | (0xFFFFFFFFu - static_cast<uint32_t>(v));
+    };
+    const int32_t max_lo = static_cast<int32_t>(a.totals[kEccMaxLo]), min_hi = static_cast<int32_t>(a.totals[kEccMinHi]);
+    std::vector<uint64_t> by_hi, by_lo;
+    for (int64_t v = 0; v < a.g.n; ++v) {
+      if (!(a.state[v] & kEccLive)) continue;
+      if ((a.target == EccTarget::Diameter && a.hi[v] <= max_lo) || (a.target == EccTarget::Radius && a.lo[v] >= min_hi)) {
+        a.state[v] &= ~kEccLive;
+        continue;
+      }
+      if (a.first) {
+        by_lo.push_back(key(a.deg[v], v));
+      } else {
+        by_hi.push_back(key(static_cast<uint32_t>(a.hi[v]), v));
+        by_lo.push_back(key(static_cast<uint32_t>(INT32_MAX - a.lo[v]), v));
+      }
+    }
+    const int64_t live = static_cast<int64_t>(by_lo.size());
+    auto best = [](std::vector<uint64_t>& keys, size_t k) {
+      k = std::min(k, keys.size());
+      std::partial_sort(keys.begin(), keys.begin() + static_cast<std::ptrdiff_t>(k), keys.end(), std::greater<uint64_t>());
+      keys.resize(k);
+    };
+    best(by_hi, kEccSelHi);
+    // (the second list skips the first's vertices: kEccSelHi more of them cover that)
+    best(by_lo, static_cast<size_t>(kMsSources) + by_hi.size());
+    int64_t k = 0;
+    for (uint64_t x : by_hi) a.sel_out[1 + k++] = 0xFFFFFFFFu - static_cast<uint32_t>(x);
+    const int64_t n_hi = k;
+    for (uint64_t x : by_lo) {
+      const int64_t v = 0xFFFFFFFFu - static_cast<uint32_t>(x);
+      if (k == kMsSources) break;
+      if (std::find(a.sel_out + 1, a.sel_out + 1 + n_hi, v) == a.sel_out + 1 + n_hi) a.sel_out[1 + k++] = v;
+    }
+    a.sel_out[0] = k;
+    for (int64_t i = k; i < kMsSources; ++i) a.sel_out[1 + i] = -1;
+    a.sel_out[1 + kMsSources] = live;
+  }
+  void ecc_update(const EccArgs& a) override {
+    const int none = ms_unreached(a.m.lvl_bytes);
+    for (int64_t v = 0; v < a.g.n; ++v) {
+      if (!(a.state[v] & kEccLive)) continue;
+      int32_t lo = a.lo[v], hi = a.hi[v];
+      for (int s = 0; s < a.m.k; ++s) {
+        const int d = level_at(a.m, v, s);
+        if (d == none) continue;
+        lo = std::max(lo, std::max(d, a.ecc[s] - d));
+        hi = std::min(hi, a.ecc[s] + d);
+      }
+      a.lo[v] = lo;
+      a.hi[v] = hi;
+      if (lo >= hi) a.state[v] = (a.state[v] & ~kEccLive) | kEccSettled;
+    }
+  }
+  void ecc_totals(const EccArgs& a) override {
+    int64_t t[kEccTotals] = {};
+    t[kEccMaxLo] = -1;
+    t[kEccMinHi] = INT32_MAX;
+    for (int64_t v = 0; v < a.g.n; ++v) {
+      const uint32_t st = a.state[v];
+      if (!(st & kEccScope)) continue;
+      ++t[kEccScopeSize];
+      t[kEccLiveN] += (st & kEccLive) ? 1 : 0;
+      if (st & kEccSettled) {
+        ++t[kEccSettledN];
+        t[kEccAtHi] += a.lo[v] == a.count_hi ? 1 : 0;
+        t[kEccAtLo] += a.lo[v] == a.count_lo ? 1 : 0;
+      }
+      t[kEccMaxLo] = std::max<int64_t>(t[kEccMaxLo], a.lo[v]);
+      t[kEccMinHi] = std::min<int64_t>(t[kEccMinHi], a.hi[v]);
+    }
+    std::copy(t, t + kEccTotals, a.totals);
+  }
   void ms_bc_forward(const MsBcArgs& a) override {
     bc_value_type(a, [&](auto val) {
       using V = decltype(val);

@@ -268,6 +268,11 @@ class HipBackend final : public Backend {
   void scc_backward(const SccArgs& a) override { on(); kern::scc_backward(a, st_); chk(); }
   void scc_end_round(const SccArgs& a) override { on(); kern::scc_end_round(a, st_); chk(); }
   void scc_relabel(const SccArgs& a) override { on(); kern::scc_relabel(a, st_); chk(); }
+  void ecc_degrees(const EccArgs& a) override { on(); kern::ecc_degrees(a, st_); chk(); }
+  void ecc_init(const EccArgs& a) override { on(); kern::ecc_init(a, st_); chk(); }
+  void ecc_select(const EccArgs& a) override { on(); kern::ecc_select(a, st_); chk(); }
+  void ecc_update(const EccArgs& a) override { on(); kern::ecc_update(a, st_); chk(); }
+  void ecc_totals(const EccArgs& a) override { on(); kern::ecc_totals(a, st_); chk(); }
   void widen_levels(const uint8_t* in, lvl_t* out, int64_t n, uint8_t base) override {
     on();
     kern::widen_levels(in, out, n, base, st_);

@@ -80,6 +80,11 @@ struct Args {
   std::string strong_components_out;  // ... the labels, one per line
   int64_t scc_trim_rounds = -2;       // --scc-trim-rounds N (EngineOptions::scc_trim_rounds; -2: the default)
   bool scc_pivot = true;              // --no-scc-pivot clears it (EngineOptions::scc_pivot)
+  bool eccentricities = false;        // --eccentricities: eccentricity bounding before the traversals (Engine::eccentricities)
+  std::string ecc_target = "all";     // --ecc-target all|diameter|radius
+  std::string ecc_component = "largest";  // --ecc-component largest|all|LABEL
+  int64_t ecc_max_passes = -1;        // --ecc-max-passes N (-1: no cap)
+  std::string eccentricities_out;     // ... the eccentricities, one per line (-1: out of scope or unsettled)
   bool mode_given = false;            // --mode on the command line (--directed turns only the default into td)
   std::vector<std::pair<std::string, double>> opts;  // --opt name=value, in order (set_engine_option)
 };
@@ -108,6 +113,14 @@ struct Args {
                "                   graph: its connected components)\n"
                "       --scc-trim-rounds N (trim sweeps per round at most; -1: to the fixed point, the default; 0: no trim)\n"
                "       --no-scc-pivot (colour every vertex in the first round instead of one high-degree pivot)\n"
+               "       --eccentricities [--eccentricities-out FILE] (exact eccentricities by bounding over 64-source batch\n"
+               "                   passes, before the traversals, after --components: diameter, radius, centre, periphery;\n"
+               "                   undirected graphs only; checked against one sequential traversal per vertex, or per\n"
+               "                   sampled vertex on a large scope, unless --no-oracle)\n"
+               "       --ecc-target all|diameter|radius (stop once every vertex is settled, or once that value is known)\n"
+               "       --ecc-component largest|all|LABEL (the vertices answered for: the largest component, every vertex,\n"
+               "                   or the component with that label)\n"
+               "       --ecc-max-passes N (at most N passes: bounds as they stand, exact 0)\n"
                "       --levels-out FILE  --cache FILE (write binary CSR)  --json  --quiet  --phase-timing\n"
                "       --directed (edge list as directed u->v pairs, like the reference's stdin reader;\n"
                "                   top-down modes only; --batch and --validate work on the in-edge shard,\n"
@@ -167,6 +180,11 @@ Args parse(int argc, char** argv) {
     else if (s == "--strong-components-out") a.strong_components_out = next();
     else if (s == "--scc-trim-rounds") a.scc_trim_rounds = std::stoll(next());
     else if (s == "--no-scc-pivot") a.scc_pivot = false;
+    else if (s == "--eccentricities") a.eccentricities = true;
+    else if (s == "--ecc-target") a.ecc_target = next();
+    else if (s == "--ecc-component") a.ecc_component = next();
+    else if (s == "--ecc-max-passes") a.ecc_max_passes = std::stoll(next());
+    else if (s == "--eccentricities-out") a.eccentricities_out = next();
     else if (s == "--no-oracle") a.oracle = false;
     else if (s == "--validate") a.validate = true;
     else if (s == "--levels-out") a.levels_out = next();
@@ -225,6 +243,18 @@ Args parse(int argc, char** argv) {
   if (!a.strong_components_out.empty() && !a.strong_components)
     usage("--strong-components-out needs --strong-components");
   if (a.scc_trim_rounds < -2) usage("--scc-trim-rounds must be >= -1");
+  if (!a.eccentricities_out.empty() && !a.eccentricities) usage("--eccentricities-out needs --eccentricities");
+  if (a.eccentricities) {
+    if (a.directed) usage("--eccentricities needs an undirected graph");
+    if (a.ecc_target != "all" && a.ecc_target != "diameter" && a.ecc_target != "radius")
+      usage("--ecc-target must be all, diameter or radius");
+    if (a.ecc_component != "largest" && a.ecc_component != "all") {
+      char* end = nullptr;
+      const long long label = std::strtoll(a.ecc_component.c_str(), &end, 10);
+      if (!end || *end || a.ecc_component.empty() || label < 0) usage("--ecc-component must be largest, all or a label");
+    }
+    if (a.ecc_max_passes < -1) usage("--ecc-max-passes must be >= 0");
+  }
   if (a.directed) {
     // a single-source traversal is top-down only (the bottom-up kernels take
     // their degrees from their own rows); --batch pulls over the in-edge shard
@@ -707,6 +737,94 @@ int main(int argc, char** argv) {
                       static_cast<long long>(c.singletons), static_cast<long long>(c.trimmed),
                       static_cast<long long>(c.rounds), c.ms, c.trim_ms, c.colour_ms, static_cast<long long>(c.sweeps),
                       static_cast<long long>(c.pivot));
+      }
+    }
+
+    // ---- eccentricities (--eccentricities), before the traversals ----
+    if (a.eccentricities) {
+      EccOptions eo_ecc;
+      eo_ecc.target = parse_ecc_target(a.ecc_target);
+      eo_ecc.component = a.ecc_component == "largest" ? EccOptions::kLargest
+                         : a.ecc_component == "all"   ? EccOptions::kAll
+                                                      : std::stoll(a.ecc_component);
+      eo_ecc.max_passes = a.ecc_max_passes;
+      std::vector<EccResult> eres(static_cast<size_t>(nlocal));
+      std::vector<int32_t> ecc, lo, hi;
+      run_ranks(ranks, [&](int i, RankCtx& rc) {
+        eres[i] = rc.engine->eccentricities(eo_ecc);
+        if (i == 0 && leader && ((a.oracle && have_host) || !a.eccentricities_out.empty())) {
+          ecc = rc.engine->gather_eccentricities();
+          rc.engine->gather_eccentricity_bounds(lo, hi);
+        }
+      }, vgroup.get());
+      if (leader) {
+        const EccResult& c = eres[0];
+        std::printf("eccentricities diameter %lld radius %lld centre %lld periphery %lld settled %lld of %lld passes %lld "
+                    "sources %lld exact %d ms %.3f\n",
+                    static_cast<long long>(c.diameter), static_cast<long long>(c.radius), static_cast<long long>(c.centre),
+                    static_cast<long long>(c.periphery), static_cast<long long>(c.settled),
+                    static_cast<long long>(c.scope_size), static_cast<long long>(c.passes),
+                    static_cast<long long>(c.sources), c.exact ? 1 : 0, c.ms);
+        if (a.oracle && have_host) {
+          // One traversal per vertex while scope x entries is small; past that,
+          // 16 settled vertices chosen by the seed, one traversal each.
+          // (DBFS_ECC_ORACLE_LIMIT: the threshold, for the tests of the sampled branch)
+          double limit = 4294967296.0;
+          if (const char* e = std::getenv("DBFS_ECC_ORACLE_LIMIT"))
+            if (*e) limit = std::atof(e);
+          auto wrong = [&](int64_t v, long long got, long long exp) {
+            std::printf("eccentricity %lld %lld %lld\n", static_cast<long long>(v), got, exp);
+            std::printf("Wrong output!\n");
+            return 1;
+          };
+          if (static_cast<double>(c.scope_size) * static_cast<double>(full.col.size()) <= limit) {
+            const std::vector<int32_t> exp = cpu_eccentricities(full);
+            int64_t dia = -1, rad = INT32_MAX;
+            for (int64_t v = 0; v < n; ++v) {
+              if (lo[v] < 0) continue;  // (out of scope)
+              if (ecc[v] >= 0 && ecc[v] != exp[v]) return wrong(v, ecc[v], exp[v]);
+              if (lo[v] > exp[v] || hi[v] < exp[v]) return wrong(v, lo[v], exp[v]);
+              dia = std::max<int64_t>(dia, exp[v]);
+              rad = std::min<int64_t>(rad, exp[v]);
+            }
+            if (c.exact && c.scope_size > 0) {
+              if (eo_ecc.target != EccTarget::Radius && c.diameter != dia) return wrong(-1, c.diameter, dia);
+              if (eo_ecc.target != EccTarget::Diameter && c.radius != rad) return wrong(-2, c.radius, rad);
+            }
+            if (!a.quiet) std::printf("Eccentricities OK!\n");
+          } else {
+            std::vector<int64_t> settled;
+            for (int64_t v = 0; v < n; ++v)
+              if (ecc[v] >= 0) settled.push_back(v);
+            std::mt19937_64 pick(a.seed * 104729 + 5);
+            for (int t = 0; t < 16 && !settled.empty(); ++t) {
+              const int64_t v = settled[pick() % settled.size()];
+              const CpuBfsResult r = cpu_bfs(full, v);
+              int64_t deepest = 0;
+              for (lvl_t l : r.level)
+                if (l != kUnreached) deepest = std::max<int64_t>(deepest, l);
+              if (ecc[v] != deepest) return wrong(v, ecc[v], deepest);
+            }
+            if (!a.quiet) std::printf("Eccentricities OK! (16 sampled)\n");
+          }
+        }
+        if (!a.eccentricities_out.empty()) {
+          std::FILE* f = std::fopen(a.eccentricities_out.c_str(), "w");
+          DBFS_CHECK(f != nullptr, "cannot write " + a.eccentricities_out);
+          for (int32_t e : ecc) std::fprintf(f, "%d\n", e);
+          std::fclose(f);
+        }
+        if (a.json)
+          std::printf("{\"graph\":\"%s\",\"n\":%lld,\"ranks\":%d,\"diameter\":%lld,\"radius\":%lld,\"centre\":%lld,"
+                      "\"periphery\":%lld,\"settled\":%lld,\"scope_size\":%lld,\"passes\":%lld,\"sources\":%lld,"
+                      "\"exact\":%s,\"wide_levels\":%s,\"ecc_target\":\"%s\",\"ms\":%.6f,\"bfs_ms\":%.6f,"
+                      "\"bound_ms\":%.6f,\"select_ms\":%.6f}\n",
+                      gname.c_str(), static_cast<long long>(n), P, static_cast<long long>(c.diameter),
+                      static_cast<long long>(c.radius), static_cast<long long>(c.centre),
+                      static_cast<long long>(c.periphery), static_cast<long long>(c.settled),
+                      static_cast<long long>(c.scope_size), static_cast<long long>(c.passes),
+                      static_cast<long long>(c.sources), c.exact ? "true" : "false", c.wide_levels ? "true" : "false",
+                      a.ecc_target.c_str(), c.ms, c.bfs_ms, c.bound_ms, c.select_ms);
       }
     }
 

@@ -693,12 +693,13 @@ void Engine::read_level_stats(int64_t* host_stats) {
 // a device-check violation (the run fails when it ends; file=td_kernels or
 // file=bu_kernels: in that kernel file's word instead of bfs_kernels'; every
 // other *_device kind records in the word of the file its phase's kernels
-// live in: ms_kernels, ms_bc_kernels, cc_kernels, scc_kernels, graph_kernels), `batch_device` the
+// live in: ms_kernels, ms_bc_kernels, cc_kernels, scc_kernels, ecc_kernels, graph_kernels), `batch_device` the
 // same at level L of a batch pass (run_batch fails after the pass), `bc_device`
 // the same during a pass's dependency accumulation (run_batch(betweenness)
 // fails after it), `cc_device` the same during the link of components()
 // (which fails when it ends), `scc_device` the same during the first trim of
-// strong_components() (which fails when it ends),
+// strong_components() (which fails when it ends), `ecc_device` the same after
+// the first bound update of eccentricities() (which fails when it ends),
 // `in_edges_device` during DeviceGraph::build_in_edges, `delay` enqueues the
 // level ms late; kind=late_wg[,us=U] (every rank, every level) makes the
 // workgroups of a sparse top-down level that take no ticket start U us late
@@ -735,8 +736,8 @@ FaultSpec FaultSpec::from_env() {
   DBFS_CHECK(f.kind == "throw" || f.kind == "exit" || f.kind == "hang" || f.kind == "device" || f.kind == "delay" ||
                  f.kind == "rccl_init" || f.kind == "peer_init" || f.kind == "late_wg" || f.kind == "batch_device" ||
                  f.kind == "in_edges_device" || f.kind == "bc_device" || f.kind == "cc_device" ||
-                 f.kind == "scc_device",
-             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|bc_device|cc_device|scc_device|in_edges_device|delay|rccl_init|"
+                 f.kind == "scc_device" || f.kind == "ecc_device",
+             "DBFS_FAULT_INJECT: kind must be throw|exit|hang|device|batch_device|bc_device|cc_device|scc_device|ecc_device|in_edges_device|delay|rccl_init|"
              "peer_init|late_wg");
   DBFS_CHECK(!file_given || f.kind == "device", "DBFS_FAULT_INJECT: file applies to kind=device only");
   // (rccl_init / peer_init: the communicators' setup fails -- NcclComm /
@@ -773,7 +774,7 @@ void Engine::inject_batch_fault(int level) {
 
 void Engine::inject_fault(int level) {
   if (fault_.kind == "batch_device" || fault_.kind == "in_edges_device" || fault_.kind == "bc_device" ||
-      fault_.kind == "cc_device" || fault_.kind == "scc_device")
+      fault_.kind == "cc_device" || fault_.kind == "scc_device" || fault_.kind == "ecc_device")
     return;  // (not a traversal's)
   if (fault_.rank != comm_.rank() || fault_.level != level) return;
   if (fault_.kind == "device") {

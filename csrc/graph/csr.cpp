@@ -105,6 +105,38 @@ std::vector<int64_t> cpu_components(const HostCSR& g) {
   return label;
 }
 
+// One queue traversal per vertex, sequential and plain: the deepest level it
+// reaches is the vertex's eccentricity within its component.  `mark` holds the
+// traversal that last saw a vertex, so no array is cleared between two of them
+// and a traversal costs its component only.  Test sizes.
+std::vector<int32_t> cpu_eccentricities(const HostCSR& g) {
+  DBFS_CHECK(g.row_lo == 0 && g.rows == g.n, "cpu_eccentricities expects a full CSR");
+  const size_t n = static_cast<size_t>(g.n);
+  std::vector<int32_t> ecc(n, 0), dist(n, 0);
+  std::vector<int64_t> mark(n, -1);
+  std::vector<vid_t> q;
+  for (int64_t s = 0; s < g.n; ++s) {
+    q.clear();
+    q.push_back(static_cast<vid_t>(s));
+    mark[s] = s;
+    dist[s] = 0;
+    int32_t deepest = 0;
+    for (size_t head = 0; head < q.size(); ++head) {
+      const vid_t u = q[head];
+      for (eid_t e = g.row_off[u]; e < g.row_off[u + 1]; ++e) {
+        const vid_t v = g.col[e];
+        if (mark[v] == s) continue;
+        mark[v] = s;
+        dist[v] = dist[u] + 1;
+        deepest = dist[v];  // (levels leave the queue in order: the last one set is the deepest)
+        q.push_back(v);
+      }
+    }
+    ecc[s] = deepest;
+  }
+  return ecc;
+}
+
 // Tarjan's algorithm with the recursion as an explicit stack of (vertex, next
 // entry) frames; a component is popped when its root's frame ends, and gets
 // the smallest id among the popped.  Shares nothing with the backends' sweeps.

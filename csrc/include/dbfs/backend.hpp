@@ -32,11 +32,12 @@ enum class DeviceKind { CPU, HIP };
 // Device-checked build: the kernel files that record bounds violations, each
 // in a word of its own (the codes of two files may coincide: a violation is
 // reported with its file).
-enum class CheckFile { Bfs, Td, Bu, Ms, MsBc, Cc, Graph, Scc };
-constexpr int kCheckFiles = 8;
+enum class CheckFile { Bfs, Td, Bu, Ms, MsBc, Cc, Graph, Scc, Ecc };
+constexpr int kCheckFiles = 9;
 inline const char* check_file_name(CheckFile f) {
   constexpr const char* names[kCheckFiles] = {"bfs_kernels", "td_kernels",  "bu_kernels",   "ms_kernels",
-                                              "ms_bc_kernels", "cc_kernels", "graph_kernels", "scc_kernels"};
+                                              "ms_bc_kernels", "cc_kernels", "graph_kernels", "scc_kernels",
+                                              "ecc_kernels"};
   return names[static_cast<int>(f)];
 }
 
@@ -1381,6 +1382,71 @@ struct SccArgs {
   vid_t* relabel_min = nullptr;    // HIP: one word
 };
 
+// Eccentricity bounding (Engine::eccentricities; Takes and Kosters): lower and
+// upper bounds of every vertex's eccentricity, tightened from the level
+// matrix of 64-source batch passes until they meet.  lo, hi and state have one
+// entry per vertex of the whole graph (several ranks: every rank its own
+// replica, updated in full from the all-gathered matrix, so all replicas stay
+// equal); state is kEccScope (the call answers for v) | kEccLive (v may still
+// be chosen as a source and is still updated) | kEccSettled (lo == hi is v's
+// eccentricity).  Integers only.
+//   ecc_degrees  deg_own[r] = stored entries of owned row r (the first pass's key).
+//   ecc_init     every v < g.n: in scope (scope_all, or comp[v] == label) lo = 0,
+//     hi = INT32_MAX and live -- a row without entries settled at 0 instead;
+//     out of scope: state 0, lo = hi = -1.
+//   ecc_select   first drops (clears kEccLive of) every live v the target no
+//     longer needs, by the totals of the last ecc_totals: diameter hi[v] <=
+//     totals[kEccMaxLo], radius lo[v] >= totals[kEccMinHi].  Then picks at
+//     most kMsSources distinct live vertices.  first: those of largest deg, ties
+//     to the smaller id.  Later: the kEccSelHi of largest hi (ties to the smaller
+//     id), then among the rest those of smallest lo (ties to the smaller id)
+//     until kMsSources are chosen.  Every key is (value << 32) | ~id, unique, so
+//     the choice does not depend on the order vertices are looked at.
+//     sel_out[0] = how many, sel_out[1 ..] their ids in that order,
+//     sel_out[1 + kMsSources] = the live vertices left after the drop.
+//   ecc_update   every live v and source s < m.k whose level d = lvl[v][s] is
+//     reached: lo[v] = max(lo[v], d, ecc[s] - d), hi[v] = min(hi[v], ecc[s] + d);
+//     bounds that meet settle v (live off, settled on).  Rows of vertices that
+//     are not live are not read.
+//   ecc_totals   over the scope: totals[kEccScopeSize], [kEccSettledN],
+//     [kEccLiveN], [kEccMaxLo], [kEccMinHi], and the settled vertices with lo ==
+//     count_hi ([kEccAtHi]: the periphery) and == count_lo ([kEccAtLo]: the centre).
+constexpr uint32_t kEccScope = 1u, kEccLive = 2u, kEccSettled = 4u;
+constexpr int kEccSelHi = 32;
+enum EccTotal { kEccScopeSize = 0, kEccSettledN, kEccLiveN, kEccMaxLo, kEccMinHi, kEccAtHi, kEccAtLo, kEccTotals };
+enum class EccTarget { All, Diameter, Radius };
+// HIP: workgroups at most of ecc_totals (a slot of kEccTotals each) and of
+// ecc_select (a slot of kEccSelSlot keys each: its kEccSelHi best by hi, its
+// kMsSources best by lo or degree, its live count).
+constexpr int kEccTotalsGrid = 1024;
+constexpr int kEccSelGrid = 256;
+constexpr int kEccSelSlot = kEccSelHi + kMsSources + 1;
+constexpr int kEccSelOut = kMsSources + 2;
+struct EccArgs {
+  ShardView g;                     // the owned rows (lo, rows, row_off) and n
+  int32_t* lo = nullptr;           // g.n entries each
+  int32_t* hi = nullptr;
+  uint32_t* state = nullptr;
+  const uint32_t* deg = nullptr;   // every vertex's stored degree (several ranks: the all-gathered deg_own slices)
+  uint32_t* deg_own = nullptr;     // ecc_degrees: g.rows entries
+  // ecc_init
+  const vid_t* comp = nullptr;     // components() labels (nullptr with scope_all)
+  bool scope_all = false;
+  vid_t label = 0;
+  // ecc_select
+  bool first = false;
+  EccTarget target = EccTarget::All;
+  unsigned long long* sel_slots = nullptr;  // HIP: kEccSelGrid x kEccSelSlot
+  int64_t* sel_out = nullptr;               // kEccSelOut
+  // ecc_update
+  MsPassMatrix m;
+  int32_t ecc[kMsSources] = {};    // the sources' eccentricities (depth - 1)
+  // ecc_totals
+  int32_t count_hi = -1, count_lo = -1;
+  int64_t* totals = nullptr;       // kEccTotals
+  int64_t* slots = nullptr;        // HIP: kEccTotalsGrid x kEccTotals
+};
+
 // ---- backend ----------------------------------------------------------------
 
 class Backend {
@@ -1621,6 +1687,12 @@ class Backend {
   virtual void scc_backward(const SccArgs& a) = 0;
   virtual void scc_end_round(const SccArgs& a) = 0;
   virtual void scc_relabel(const SccArgs& a) = 0;
+  // eccentricity bounding (EccArgs)
+  virtual void ecc_degrees(const EccArgs& a) = 0;
+  virtual void ecc_init(const EccArgs& a) = 0;
+  virtual void ecc_select(const EccArgs& a) = 0;
+  virtual void ecc_update(const EccArgs& a) = 0;
+  virtual void ecc_totals(const EccArgs& a) = 0;
 
  protected:
   std::function<void(double)> wait_watch_;

@@ -577,6 +577,37 @@ struct SccResult {
   double colour_ms = 0.0;      // the colouring rounds (forward and backward sweeps)
 };
 
+// Engine::eccentricities.
+struct EccOptions {
+  EccTarget target = EccTarget::All;
+  // the vertices the call answers for: kLargest the largest connected
+  // component, kAll every vertex, a value >= 0 the component with that label
+  static constexpr int64_t kLargest = -2, kAll = -1;
+  int64_t component = kLargest;
+  int64_t max_passes = -1;  // < 0: no cap
+};
+EccTarget parse_ecc_target(const std::string& s);
+
+struct EccResult {
+  // the largest lower bound / the smallest upper bound over the scope: with
+  // target All and exact, the diameter and the radius; target Diameter
+  // promises `diameter` only (radius is then an upper bound), Radius `radius`
+  // only (diameter a lower bound)
+  int64_t diameter = 0, radius = 0;
+  int64_t centre = 0;      // settled vertices with eccentricity == radius
+  int64_t periphery = 0;   // ... == diameter
+  int64_t passes = 0;      // batch passes run
+  int64_t sources = 0;     // traversals in them
+  int64_t settled = 0;     // in-scope vertices whose bounds met
+  int64_t scope_size = 0;
+  bool exact = false;      // the loop ended by itself, not by max_passes
+  bool wide_levels = false;
+  double ms = 0.0;         // wall time, max over ranks: the three parts and the set-up
+  double bfs_ms = 0.0;     // the batch passes (several ranks: the matrix all-gather too)
+  double bound_ms = 0.0;   // ecc_update and ecc_totals
+  double select_ms = 0.0;  // ecc_select and its copy to the host
+};
+
 // Fault injection for failure-detection tests (see Engine::inject_fault).
 struct FaultSpec {
   int rank = -1, level = -1;
@@ -711,6 +742,36 @@ class Engine {
   std::vector<int64_t> gather_strong_component_sizes();
   bool has_strong_components() const { return scc_ && scc_->valid; }
   const SccResult& last_strong_components() const;
+  // Exact eccentricities by bounding (Takes and Kosters); collective,
+  // undirected graphs only.  ecc(v) = the largest distance from v within its
+  // connected component (0 for a vertex without neighbours; stored duplicates
+  // and self-loops change nothing).  A loop of batch passes
+  // (csrc/engine/eccentricity.cpp): select at most 64 live sources on the
+  // device (Backend::ecc_select), traverse from all of them at once
+  // (run_batch_pass, levels kept), tighten every live vertex's bounds from
+  // the pass's level matrix (Backend::ecc_update: a source s with eccentricity
+  // e at distance d gives max(d, e - d) <= ecc(v) <= e + d), until every
+  // in-scope vertex is settled (target All) or the target's value is known.
+  // Every pass settles at least its own sources, so the loop ends; max_passes
+  // ends it early with exact = false and valid bounds.  components() runs
+  // first if the scope needs its labels and it has not run.  Several ranks,
+  // the simple form: pass_matrix all-gathers the level matrix, every rank
+  // holds and updates the bounds of all n vertices and so selects the same
+  // sources with no further exchange -- correct, not fast.  Device state: 16 B
+  // per vertex of the whole graph (lo, hi, state, degree), allocated by the
+  // first call and kept; apart from run / validate / components state.  The
+  // call uses the batch buffers: it collects a pending batch's levels first,
+  // and its passes replace the resident batch pass (validate_batch_pass then
+  // needs a new run_batch).
+  EccResult eccentricities(const EccOptions& o = {});
+  // The last eccentricities() call's bounds for all n vertices (this rank's
+  // replica: no communication): lo and hi, (-1, -1) out of scope, hi =
+  // INT32_MAX where no source reached the vertex; and the eccentricities, -1
+  // where out of scope or unsettled.  Throw when eccentricities() has not run.
+  void gather_eccentricity_bounds(std::vector<int32_t>& lo, std::vector<int32_t>& hi);
+  std::vector<int32_t> gather_eccentricities();
+  bool has_eccentricities() const { return ecc_ && ecc_->valid; }
+  const EccResult& last_eccentricities() const;
   // Test hook: overwrite source slot `slot`'s level of global `vertex` in the
   // resident level matrix (on its owner; level < 0: unreached), so a test can
   // plant a violation for validate_batch_pass to find.
@@ -891,6 +952,18 @@ class Engine {
     SccResult last;
   };
   std::unique_ptr<SccBuffers> scc_;
+  // eccentricity state (csrc/engine/eccentricity.cpp), allocated by the first
+  // eccentricities() call; separate from everything above
+  struct EccBuffers {
+    DBuf<int32_t> lo, hi;        // EccArgs: n entries each
+    DBuf<uint32_t> state;
+    DBuf<uint32_t> deg, deg_own; // nranks x part entries; several ranks: the owned slice
+    DBuf<unsigned long long> sel_slots;
+    DBuf<int64_t> sel_out, totals, slots;
+    bool valid = false;          // lo, hi and state hold the last call's result
+    EccResult last;
+  };
+  std::unique_ptr<EccBuffers> ecc_;
   // 0: done; 1: deeper than the level type holds (rerun wider)
   int run_batch_pass(const int64_t* src, int k, int pass, BatchDirection dir, int lvl_bytes, BatchResult& out);
   void collect_batch_levels();

@@ -97,6 +97,12 @@ CpuBfsResult cpu_bfs(const HostCSR& g, int64_t src);
 // nothing; a vertex without entries is its own component.
 std::vector<int64_t> cpu_components(const HostCSR& g);
 
+// Sequential eccentricity oracle: one queue traversal per vertex, ecc[v] = the
+// largest distance from v to a vertex of its own component over the stored
+// entries (0 for a vertex without neighbours; self-loops and duplicates
+// change nothing).  O(sum over components of size x entries): test sizes.
+std::vector<int32_t> cpu_eccentricities(const HostCSR& g);
+
 // Sequential strongly-connected-components oracle (Tarjan 1972, an explicit
 // stack instead of the recursion): label[v] = the smallest vertex id of v's
 // strongly connected component over the stored entries u -> w.  Self-loops

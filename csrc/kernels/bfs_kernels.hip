@@ -772,6 +772,7 @@ void inject_check_failure(CheckFile f, hipStream_t st) {
     case CheckFile::Cc: inject_check_cc(st); break;
     case CheckFile::Graph: inject_check_graph(st); break;
     case CheckFile::Scc: inject_check_scc(st); break;
+    case CheckFile::Ecc: inject_check_ecc(st); break;
   }
 }
 
@@ -779,14 +780,14 @@ void inject_check_failure(CheckFile f, hipStream_t st) {
 // checked build that leaves one out is not a checked build).
 bool checks_enabled() {
   return kCheckedLocal && kCheckedTd && kCheckedBu && kCheckedMs && kCheckedMsBc && kCheckedCc && kCheckedGraph &&
-         kCheckedScc;
+         kCheckedScc && kCheckedEcc;
 }
 
 unsigned long long take_check_error(CheckFile* file) {
   // (each kernel file records into its own g_check; all are read and cleared)
   const unsigned long long h[kCheckFiles] = {take_check_local(), take_check_td(), take_check_bu(), take_check_ms(),
                                              take_check_ms_bc(), take_check_cc(), take_check_graph(),
-                                             take_check_scc()};
+                                             take_check_scc(), take_check_ecc()};
   for (int i = 0; i < kCheckFiles; ++i)
     if (h[i]) {
       if (file) *file = static_cast<CheckFile>(i);

@@ -28,6 +28,7 @@ unsigned long long take_check_ms_bc();
 unsigned long long take_check_cc();
 unsigned long long take_check_graph();
 unsigned long long take_check_scc();
+unsigned long long take_check_ecc();
 void inject_check_td(hipStream_t st);
 void inject_check_bu(hipStream_t st);
 void inject_check_ms(hipStream_t st);
@@ -35,7 +36,8 @@ void inject_check_ms_bc(hipStream_t st);
 void inject_check_cc(hipStream_t st);
 void inject_check_graph(hipStream_t st);
 void inject_check_scc(hipStream_t st);
-extern const bool kCheckedTd, kCheckedBu, kCheckedMs, kCheckedMsBc, kCheckedCc, kCheckedGraph, kCheckedScc;
+void inject_check_ecc(hipStream_t st);
+extern const bool kCheckedTd, kCheckedBu, kCheckedMs, kCheckedMsBc, kCheckedCc, kCheckedGraph, kCheckedScc, kCheckedEcc;
 // A level's totals and finish from unscanned unit statistics, one workgroup
 // (bfs_kernels.hip; bottom-up levels without the fused finish).
 void totals_finish(const ScanArgs& a, hipStream_t st);

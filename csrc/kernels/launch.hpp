@@ -94,6 +94,13 @@ void scc_backward(const SccArgs& a, hipStream_t st);
 void scc_end_round(const SccArgs& a, hipStream_t st);
 void scc_relabel(const SccArgs& a, hipStream_t st);
 
+// ecc_kernels.hip (eccentricity bounding: EccArgs)
+void ecc_degrees(const EccArgs& a, hipStream_t st);
+void ecc_init(const EccArgs& a, hipStream_t st);
+void ecc_select(const EccArgs& a, hipStream_t st);
+void ecc_update(const EccArgs& a, hipStream_t st);
+void ecc_totals(const EccArgs& a, hipStream_t st);
+
 // peer_kernels.hip (PeerComm: collectives through peer-mapped windows)
 constexpr int kMaxPeers = 16;
 struct PeerPushArgs {

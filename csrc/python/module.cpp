@@ -243,6 +243,19 @@ PYBIND11_MODULE(_dbfs_native, m) {
       },
       py::arg("csr"));
 
+  // sequential eccentricity oracle: int32 [n], every vertex within its own component
+  m.def(
+      "cpu_eccentricities",
+      [](const HostCSR& g) {
+        std::vector<int32_t> r;
+        {
+          py::gil_scoped_release rel;
+          r = cpu_eccentricities(g);
+        }
+        return to_numpy(r);
+      },
+      py::arg("csr"));
+
   // sequential strongly-connected-components oracle: int64 [n], the smallest id of every vertex's SCC
   m.def(
       "cpu_strong_components",
@@ -808,6 +821,22 @@ PYBIND11_MODULE(_dbfs_native, m) {
       .def_readonly("trim_ms", &SccResult::trim_ms)
       .def_readonly("colour_ms", &SccResult::colour_ms);
 
+  py::class_<EccResult>(m, "EccentricityResult")
+      .def_readonly("diameter", &EccResult::diameter)
+      .def_readonly("radius", &EccResult::radius)
+      .def_readonly("centre", &EccResult::centre)
+      .def_readonly("periphery", &EccResult::periphery)
+      .def_readonly("passes", &EccResult::passes)
+      .def_readonly("sources", &EccResult::sources)
+      .def_readonly("settled", &EccResult::settled)
+      .def_readonly("scope_size", &EccResult::scope_size)
+      .def_readonly("exact", &EccResult::exact)
+      .def_readonly("wide_levels", &EccResult::wide_levels)
+      .def_readonly("ms", &EccResult::ms)
+      .def_readonly("bfs_ms", &EccResult::bfs_ms)
+      .def_readonly("bound_ms", &EccResult::bound_ms)
+      .def_readonly("select_ms", &EccResult::select_ms);
+
   py::class_<Engine, std::shared_ptr<Engine>>(m, "Engine")
       .def(py::init([](std::shared_ptr<DeviceGraph> g, std::shared_ptr<Comm> c, const std::string& mode, double alpha,
                        double beta, int bu_lane_limit, bool phase_timing, bool force_exchange) {
@@ -976,6 +1005,39 @@ PYBIND11_MODULE(_dbfs_native, m) {
                v = e.gather_strong_component_sizes();
              }
              return to_numpy(v);
+           })
+      // eccentricity bounding (component: -2 the largest, -1 every vertex, else a label; max_passes < 0: no cap)
+      .def(
+          "eccentricities",
+          [](Engine& e, const std::string& target, int64_t component, int64_t max_passes) {
+            EccOptions o;
+            o.target = parse_ecc_target(target);
+            o.component = component;
+            o.max_passes = max_passes;
+            py::gil_scoped_release rel;
+            return e.eccentricities(o);
+          },
+          py::arg("target") = "all", py::arg("component") = -2, py::arg("max_passes") = -1)
+      .def_property_readonly("has_eccentricities", &Engine::has_eccentricities)
+      .def("last_eccentricities", [](const Engine& e) { return e.last_eccentricities(); })
+      // the last eccentricities() call: int32 [n] (-1: out of scope or unsettled) / the bounds (lo, hi), int32 [n] each
+      .def("gather_eccentricities",
+           [](Engine& e) {
+             std::vector<int32_t> v;
+             {
+               py::gil_scoped_release rel;
+               v = e.gather_eccentricities();
+             }
+             return to_numpy(v);
+           })
+      .def("gather_eccentricity_bounds",
+           [](Engine& e) {
+             std::vector<int32_t> lo, hi;
+             {
+               py::gil_scoped_release rel;
+               e.gather_eccentricity_bounds(lo, hi);
+             }
+             return py::make_tuple(to_numpy(lo), to_numpy(hi));
            })
       .def("gather_batch_parents",
            [](Engine& e) {

@@ -165,6 +165,35 @@ class StrongComponentsResult:
                 f"rounds={self.rounds}, sweeps={self.sweeps}, pivot={self.pivot}, ms={self.ms:.4f})")
 
 
+class EccentricityResult:
+    """Eccentricities by bounding (``BFS.eccentricities``): ``diameter`` (the
+    largest lower bound over the scope) and ``radius`` (the smallest upper
+    bound) -- with target ``"all"`` and ``exact`` the scope's diameter and
+    radius; target ``"diameter"`` promises ``diameter`` only (``radius`` is then
+    an upper bound) and ``"radius"`` the reverse; ``centre`` / ``periphery``
+    (settled vertices whose eccentricity equals ``radius`` / ``diameter``),
+    ``passes`` (batch passes run) and ``sources`` (traversals in them),
+    ``settled`` of ``scope_size`` in-scope vertices, ``exact`` (the loop ended
+    by itself, not by ``max_passes``), ``wide_levels`` (a pass needed 16-bit
+    levels), ``ms`` (wall time, max over ranks) with its ``bfs_ms`` (the
+    passes), ``bound_ms`` (bound updates and totals) and ``select_ms`` (source
+    selection) parts."""
+
+    __slots__ = ("diameter", "radius", "centre", "periphery", "passes", "sources", "settled", "scope_size", "exact",
+                 "wide_levels", "ms", "bfs_ms", "bound_ms", "select_ms")
+
+    def __init__(self, r: Any):
+        for name in self.__slots__[:8]:
+            setattr(self, name, int(getattr(r, name)))
+        self.exact, self.wide_levels = bool(r.exact), bool(r.wide_levels)
+        self.ms, self.bfs_ms, self.bound_ms, self.select_ms = float(r.ms), float(r.bfs_ms), float(r.bound_ms), float(r.select_ms)
+
+    def __repr__(self) -> str:
+        return (f"EccentricityResult(diameter={self.diameter}, radius={self.radius}, centre={self.centre}, "
+                f"periphery={self.periphery}, settled={self.settled}/{self.scope_size}, passes={self.passes}, "
+                f"sources={self.sources}, exact={self.exact}, ms={self.ms:.4f})")
+
+
 class BFS:
     """Distributed BFS over a graph given as a HostCSR, generator params, or a file path."""
 
@@ -445,6 +474,56 @@ class BFS:
     def strong_component_sizes(self) -> np.ndarray:
         """int64 [n]: entry v is the number of vertices in v's strongly connected component (last strong_components())."""
         return self.engine.gather_strong_component_sizes()
+
+    def eccentricities(self, target: str = "all", component="largest",
+                       max_passes: Optional[int] = None) -> EccentricityResult:
+        """Exact eccentricities, diameter and radius by eccentricity bounding
+        (Takes and Kosters) over 64-source batch passes (collective;
+        undirected graphs only -- a directed engine raises).  ecc(v) is the
+        largest distance from v within its connected component: 0 for a vertex
+        without neighbours, stored duplicates and self-loops change nothing.
+        ``component`` is the scope the call answers for: ``"largest"`` the
+        largest component, an int the component with that label, ``"all"``
+        every vertex (components() runs first if the first two need it).
+        ``diameter`` / ``radius`` are the max / min of ecc over the scope: with
+        ``"all"`` and a vertex without neighbours the radius is 0.  ``target``:
+        ``"all"`` runs until every in-scope vertex is settled; ``"diameter"``
+        drops a vertex once its upper bound is no larger than the largest
+        lower bound and returns that bound, ``"radius"`` drops one once its
+        lower bound is no smaller than the smallest upper bound -- dropped
+        vertices stay unsettled with valid bounds.  Every pass picks the 64
+        live vertices with the widest bounds (first pass: the largest
+        degrees), traverses from all at once and tightens every live vertex's
+        bounds from the level matrix; it settles at least its own sources, so
+        the loop ends -- a cycle needs a traversal per vertex, n / 64 passes.
+        ``max_passes`` ends it early: ``exact`` is then False and the bounds
+        stand as they are, nothing raises.  Several ranks hold and update all
+        n bounds each, from the all-gathered level matrix: correct, not fast.
+        16 bytes per vertex of the whole graph on the device, kept.  run /
+        levels(), components() and a later run_batch are left alone; the
+        call's passes replace the resident batch pass (validate_batch_pass
+        needs a new run_batch)."""
+        if isinstance(component, str):
+            if component not in ("largest", "all"):
+                raise ValueError('component must be "largest", "all" or a component label')
+            scope = -2 if component == "largest" else -1
+        else:
+            scope = int(component)
+            if scope < 0:
+                raise ValueError('component must be "largest", "all" or a component label')
+        if target not in ("all", "diameter", "radius"):
+            raise ValueError('target must be "all", "diameter" or "radius"')
+        return EccentricityResult(self.engine.eccentricities(
+            target, scope, -1 if max_passes is None else max(0, int(max_passes))))
+
+    def eccentricity(self) -> np.ndarray:
+        """int32 [n]: the last eccentricities() call's values, -1 where out of scope or unsettled."""
+        return self.engine.gather_eccentricities()
+
+    def eccentricity_bounds(self):
+        """(lo, hi), int32 [n] each: the last eccentricities() call's bounds;
+        (-1, -1) out of scope, hi = INT32_MAX where no source has reached the vertex."""
+        return self.engine.gather_eccentricity_bounds()
 
     def _component_roots(self, k: int, seed: int, component, strong: bool = False) -> List[int]:
         what = "strong_component" if strong else "component"

@@ -95,6 +95,13 @@ def cpu_strong_components(csr):
     return N.cpu_strong_components(csr)
 
 
+def cpu_eccentricities(csr):
+    """Sequential eccentricity oracle (one queue traversal per vertex): int32
+    [n], ecc[v] = the largest distance from v within its own component; 0 for
+    a vertex without neighbours.  Test sizes."""
+    return N.cpu_eccentricities(csr)
+
+
 def cpu_betweenness(csr, sources, directed: bool = False, path_counts: bool = False, wide_counts: bool = False):
     """Sequential Brandes oracle over the stored adjacency entries (duplicates
     are parallel edges, self-loops never lie on a shortest path): returns

@@ -215,3 +215,94 @@ def strong_component_labels_reference(csr) -> np.ndarray:
             return label
         p = int(rest[0])
         label[closure(p, u, w) & closure(p, w, u)] = p
+
+
+def _batch_levels_reference(ro, col, n, src) -> np.ndarray:
+    """Levels from up to 64 sources at once, int32 [n, k] (-1 unreached): one
+    bit per source in a word per vertex, every level one OR-reduction of the
+    neighbours' frontier words over each row (np.bitwise_or.reduceat)."""
+    k = len(src)
+    shifts = np.arange(k, dtype=np.uint64)
+    seen = np.zeros(n, dtype=np.uint64)
+    seen[src] = np.uint64(1) << shifts  # (distinct sources)
+    dist = np.full((n, k), -1, dtype=np.int32)
+    dist[src, np.arange(k)] = 0
+    has = np.diff(ro) > 0
+    starts = ro[:-1][has]
+    front = seen.copy()
+    level = 0
+    while col.size and front.any():
+        level += 1
+        acc = np.zeros(n, dtype=np.uint64)
+        # (rows without entries take no part: the starts of the others delimit exactly their entries)
+        acc[has] = np.bitwise_or.reduceat(front[col], starts)
+        new = acc & ~seen
+        idx = np.nonzero(new)[0]
+        if idx.size == 0:
+            break
+        bits = ((new[idx, None] >> shifts[None, :]) & np.uint64(1)).astype(bool)
+        sub = dist[idx]
+        sub[bits] = level
+        dist[idx] = sub
+        seen |= new
+        front = new
+    return dist
+
+
+def eccentricity_bounding_reference(csr, scope_mask, target: str = "all", max_passes: Optional[int] = None):
+    """Eccentricity bounding (Takes and Kosters) as BFS.eccentricities runs it,
+    in numpy: ``(lo, hi, settled, passes, sources_used)`` -- int32 [n] bounds
+    ((-1, -1) out of scope, hi = INT32_MAX where no source reached), the bool
+    [n] mask of settled vertices, the passes of at most 64 sources and the
+    traversals in them.  In scope: lo = 0, hi = INT32_MAX and live; a row
+    without entries is settled at 0.  Every pass first drops the live vertices
+    the target no longer needs (``"diameter"``: hi <= max lo over the scope,
+    ``"radius"``: lo >= min hi), then takes its sources among the live ones --
+    first pass: the 64 of largest stored row length, ties to the smaller id;
+    later: the 32 of largest hi (ties to the smaller id), then of the rest
+    those of smallest lo (ties to the smaller id) up to 64 in all -- traverses
+    from all of them and, for every live v and source s at distance d with
+    eccentricity e, sets lo[v] = max(lo[v], d, e - d), hi[v] = min(hi[v], e +
+    d); bounds that meet settle v.  Ends when nothing is live or after
+    ``max_passes``.  Independent of cpu_eccentricities and of the backends."""
+    if target not in ("all", "diameter", "radius"):
+        raise ValueError('target must be "all", "diameter" or "radius"')
+    ro = np.asarray(csr.row_off).astype(np.int64)
+    col = np.asarray(csr.col).astype(np.int64)
+    n = int(csr.n)
+    inf = np.iinfo(np.int32).max
+    deg = np.diff(ro)
+    scope = np.asarray(scope_mask, dtype=bool)
+    lo = np.where(scope, 0, -1).astype(np.int64)
+    hi = np.where(scope, np.where(deg == 0, 0, inf), -1).astype(np.int64)
+    settled = scope & (deg == 0)
+    live = scope & (deg > 0)
+    passes = sources_used = 0
+    while True:
+        if scope.any() and target == "diameter":
+            live &= ~(hi <= lo[scope].max())
+        if scope.any() and target == "radius":
+            live &= ~(lo >= hi[scope].min())
+        if max_passes is not None and passes >= max_passes:
+            break
+        cand = np.nonzero(live)[0]
+        if cand.size == 0:
+            break
+        if passes == 0:
+            src = cand[np.lexsort((cand, -deg[cand]))[:64]]
+        else:
+            first = cand[np.lexsort((cand, -hi[cand]))[:32]]
+            rest = np.setdiff1d(cand, first)
+            src = np.concatenate([first, rest[np.lexsort((rest, lo[rest]))[:64 - first.size]]])
+        dist = _batch_levels_reference(ro, col, n, src).astype(np.int64)
+        ecc = dist.max(axis=0)
+        d = dist[live]
+        reached = d >= 0
+        lo[live] = np.maximum(lo[live], np.where(reached, np.maximum(d, ecc[None, :] - d), 0).max(axis=1))
+        hi[live] = np.minimum(hi[live], np.where(reached, ecc[None, :] + d, inf).min(axis=1))
+        met = live & (lo >= hi)
+        settled |= met
+        live &= ~met
+        passes += 1
+        sources_used += int(src.size)
+    return lo.astype(np.int32), hi.astype(np.int32), settled, passes, sources_used
