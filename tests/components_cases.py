@@ -62,6 +62,37 @@ def _edge_list_csr():
     return dbfs.build_csr(n, u, v)
 
 
+TIER_LENGTHS = (31, 32, 33, 34, 35, 1023, 1024, 1025, 1026, 1027)
+TIER_CENTRE = 7990  # centre k has id TIER_CENTRE + k
+TIER_DECOY = 2000
+
+
+def _tiers(directed=False):
+    """Ten stars whose centres 7990 + k have exactly L leaves: L and, with the
+    sampled form's first 2 entries gone, L - 2 lie on both sides of cc_link's
+    lane tier (a range of up to 32 entries) and wave tier (up to 1024).  Every
+    star has leaves of its own among the shuffled ids 0..5289, so no centre is
+    in the largest component, whose rows the sampled form skips: that is a
+    path on the 2000 shuffled ids 5290..7289.  The rest is isolated: n = 8005.
+    Undirected, every edge is also stored in its leaf's row, which hooks it
+    whatever the centre's walk leaves out; directed (centre -> leaf only, never
+    sampled) an entry the walk of its row skips is hooked nowhere."""
+    rng = np.random.default_rng(11)
+    leaves = rng.permutation(sum(TIER_LENGTHS))
+    ends = np.cumsum(TIER_LENGTHS)
+    u = [np.full(length, TIER_CENTRE + k) for k, length in enumerate(TIER_LENGTHS)]
+    v = [leaves[e - length:e] for e, length in zip(ends, TIER_LENGTHS)]
+    decoy = leaves.size + rng.permutation(TIER_DECOY)
+    assert decoy.max() < TIER_CENTRE
+    csr = dbfs.build_csr(8005, np.concatenate(u + [decoy[:-1]]).astype(np.uint32),
+                         np.concatenate(v + [decoy[1:]]).astype(np.uint32), directed=directed)
+    deg = np.diff(np.asarray(csr.row_off))
+    assert [int(d) for d in deg[TIER_CENTRE:TIER_CENTRE + len(TIER_LENGTHS)]] == list(TIER_LENGTHS)
+    back = 0 if directed else 1  # entries of the edges' other ends
+    assert np.all(deg[:leaves.size] == back) and deg[leaves.size:TIER_CENTRE].max() == 1 + back
+    return csr
+
+
 # name -> (generator parameters | builder of a HostCSR | file path, directed)
 GRAPHS = {
     "rmat13": (dbfs.rmat_params(13, 16, 44), False),
@@ -70,6 +101,7 @@ GRAPHS = {
     "partial20000": (dbfs.uniform_params(20000, 11000, 3), False),
     "n4097": (dbfs.uniform_params(4097, 10000, 5), False),
     "ladder": (sc._ladder, False),
+    "cc_tiers": (_tiers, False),
     "grid70x60": (dbfs.grid_params(70, 60), False),
     "path_desc": (lambda: _path(np.arange(3000)[::-1]), False),
     "path_asc": (lambda: _path(np.arange(3000)), False),
@@ -85,6 +117,7 @@ GRAPHS = {
     "star_in5000": (lambda: dc.host_csr("star_in5000"), True),
     "star_out5000": (lambda: dc.host_csr("star_out5000"), True),
     "back_edge10": (lambda: dc.host_csr("back_edge10"), True),
+    "cc_tiers_out": (lambda: _tiers(directed=True), True),
 }
 # graph facts: n, components, largest (size), label (of the largest), singletons, pairs (components of size 2),
 # multi (components of size >= 2)
@@ -95,6 +128,8 @@ FACTS = {
     "partial20000": dict(n=20000, components=9016, largest=3573, label=0),
     "n4097": dict(n=4097, components=33, largest=4064),
     "ladder": dict(n=6021),
+    "cc_tiers": dict(n=8005, components=716, largest=2000, label=5290, singletons=705, multi=11),
+    "cc_tiers_out": dict(n=8005, components=716, largest=2000, label=5290, singletons=705, multi=11),
     "grid70x60": dict(n=4200, components=1, largest=4200, label=0, singletons=0),
     "path_desc": dict(n=3000, components=1, label=0),
     "path_asc": dict(n=3000, components=1, label=0),
@@ -104,10 +139,11 @@ FACTS = {
 }
 UNDIRECTED = [g for g, (_, d) in GRAPHS.items() if not d]
 DIRECTED = [g for g, (_, d) in GRAPHS.items() if d]
-HUB_SORT_BOTH = ("rmat13", "rmat10", "ladder")
-# (graph, hub_sort): every graph as the BFS builds it, the RMAT and ladder graphs also unsorted
+HUB_SORT_BOTH = ("rmat13", "rmat10", "ladder", "cc_tiers", "cc_tiers_out")
+# (graph, hub_sort): every graph as the BFS builds it, the RMAT, ladder and tier graphs also unsorted
 CASES = [(g, True) for g in GRAPHS] + [(g, False) for g in HUB_SORT_BOTH]
-RANK_CASES = ["rmat13", "sparse20000", "n4097", "ladder", "one_way_bridge", "path_desc"]
+RANK_CASES = ["rmat13", "sparse20000", "n4097", "ladder", "cc_tiers", "cc_tiers_out", "one_way_bridge",
+              "path_desc"]
 TINY_RANK_CASES = ["tiny5", "empty3"]
 
 _csr_cache = {}

@@ -426,6 +426,12 @@ def in_edges(name, P, device, hub_sort, sort_after=False, rt=None):
         shards = [body(rt or init_runtime(device))]
     else:
         shards = run_virtual_ranks(P, body, device=device)
+    in_edge_shards_are_the_transpose(csr, shards)
+
+
+def in_edge_shards_are_the_transpose(csr, shards):
+    """The (row_off, col) in-edge shards of all ranks, in rank order, against
+    the numpy transpose of the host CSR."""
     t_off, t_col = transpose(csr)
     deg = np.concatenate([np.diff(ro) for ro, _ in shards])
     col = np.concatenate([c for _, c in shards])

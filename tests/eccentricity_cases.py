@@ -139,10 +139,15 @@ def check_bounds(name, scope, lo, hi):
 
 def check_against_reference(name, scope, target, bfs, res, max_passes=None):
     """Bounds, settled set, passes and sources equal the numpy loop's."""
-    lo, hi, settled, passes, used = reference(name, scope, target, max_passes)
+    equals_bounding_reference(reference(name, scope, target, max_passes), bfs, res, f"{name} {scope} {target}")
+
+
+def equals_bounding_reference(ref, bfs, res, what):
+    """... `ref` being eccentricity_bounding_reference's tuple for the call that gave `res`."""
+    lo, hi, settled, passes, used = ref
     got_lo, got_hi = bfs.eccentricity_bounds()
     e = bfs.eccentricity()
-    assert (res.passes, res.sources) == (passes, used), f"{name} {scope} {target}"
+    assert (res.passes, res.sources) == (passes, used), what
     assert np.array_equal(got_lo, lo) and np.array_equal(got_hi, hi)
     assert np.array_equal(e >= 0, settled) and res.settled == int(settled.sum())
     assert np.array_equal(e[settled], lo[settled])

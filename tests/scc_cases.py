@@ -68,7 +68,46 @@ def _bowtie():
     return dc._csr(1403, u, v)
 
 
-_NEW = {"cycle3000_desc": _cycle_desc, "cycle_chain_asc": lambda: _cycle_chain(True),
+TIER_LENGTHS = (32, 33, 96, 97, 160)
+
+
+def tier_rows():
+    """scc_tiers' ten rows as (kind, vertex, partner, others): kind "out": the
+    vertex's out-row holds len(others) sinks and the partner; kind "in": its
+    in-row holds len(others) sources and the partner.  The other direction of
+    the pair is one arc, so {partner, vertex} is a cycle.  Ids ascend within a
+    block: others < partner < vertex."""
+    rows, at = [], 0
+    for kind in ("out", "in"):
+        for length in TIER_LENGTHS:
+            others = np.arange(at, at + length - 1)
+            rows.append((kind, at + length, at + length - 1, others))
+            at += length + 1
+    return rows
+
+
+def _tiers():
+    """Rows on scc_row_any's tiers (the first kSccLane = 32 entries by the
+    lane, the rest in 64-entry steps by the wave): out-rows and in-rows of 32,
+    33, 96, 97 and 160 entries of which all but the last, the partner's, lead
+    to sinks (from sources) that the first trim sweep settles.  Unsorted, the
+    partner -- the largest id of its row -- is entry 31, 32, 95, 96 and 159:
+    the lane's last, the wave's first, the last of a full step, the first of a
+    partial one, the last of all.  A walk that misses it trims half of a
+    2-cycle.  The partner's id is below the vertex's, so the closure too
+    reaches its root only through that entry."""
+    u, v = [], []
+    for kind, x, p, others in tier_rows():
+        a, b = np.full(others.size, x), others
+        u += [a if kind == "out" else b, [x], [p]]
+        v += [b if kind == "out" else a, [p], [x]]
+    g = dc._csr(tier_rows()[-1][1] + 1, np.concatenate(u), np.concatenate(v))
+    deg = np.diff(np.asarray(g.row_off))
+    assert [int(deg[x]) for kind, x, _, _ in tier_rows() if kind == "out"] == list(TIER_LENGTHS)
+    return g
+
+
+_NEW = {"scc_tiers": _tiers, "cycle3000_desc": _cycle_desc, "cycle_chain_asc": lambda: _cycle_chain(True),
         "cycle_chain_desc": lambda: _cycle_chain(False), "hub_cycle5000": _hub_cycle, "bowtie": _bowtie}
 DIRECTED = [g for g in dc.GRAPHS if g != "file_d6"] + ["dup_in6000"] + list(_NEW)
 UNDIRECTED = ["rmat13"]  # components_cases': the labels are the connected components'
@@ -91,16 +130,17 @@ FACTS = {
     "cycle_chain_desc": dict(n=120, components=40, largest=3, label=0, singletons=0, multi=40),
     "hub_cycle5000": dict(n=5001, components=1, largest=5001, label=0, singletons=0, multi=1),
     "bowtie": dict(n=1403, components=404, largest=1000, label=200, singletons=403, multi=1),
+    "scc_tiers": dict(n=846, components=836, largest=2, label=31, singletons=826, multi=10),
     # (the undirected graph: components_cases.FACTS["rmat13"])
     "rmat13": dict(n=8192, components=1718, largest=6474, label=2, singletons=1716, multi=2),
 }
 ACYCLIC = ("star_out5000", "star_in5000", "d_path300", "dup_in6000", "empty3")
-HUB_SORT_BOTH = ("d_rmat10", "d_rmat13")
+HUB_SORT_BOTH = ("d_rmat10", "d_rmat13", "scc_tiers")
 CASES = [(g, True) for g in GRAPHS] + [(g, False) for g in HUB_SORT_BOTH]
 # pure colouring needs about 243 000 sweeps on bowtie and 45 000 on d_path300: not run there
 FORCED_CASES = ["d_rmat10", "d_rmat13", "d_n4097", "star_out5000", "star_in5000", "one_way_bridge", "back_edge10",
-                "tiny5", "empty3", "cycle_chain_asc", "cycle_chain_desc", "hub_cycle5000", "cycle3000_desc"]
-RANK_CASES = ["d_rmat13", "one_way_bridge", "d_n4097", "cycle_chain_asc", "hub_cycle5000"]
+                "tiny5", "empty3", "cycle_chain_asc", "cycle_chain_desc", "hub_cycle5000", "cycle3000_desc", "scc_tiers"]
+RANK_CASES = ["d_rmat13", "one_way_bridge", "d_n4097", "cycle_chain_asc", "hub_cycle5000", "scc_tiers"]
 TINY_RANK_CASES = ["tiny5", "empty3"]
 
 _csr_cache = {}
